@@ -18,6 +18,13 @@ itself (WORLD_SIZE set) each rank checks WORLD_SIZE == --gpus.  One rank per GPU
             backward) as the torch-CPU sequence of BASELINE.md section 3, timed on this box's host cores over the WC
             sites of one G+D step; the float64 oracle only CHECKS its output.
 
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line: the headline figure only.
+--full adds everything else, each leg after the timed steps: the step at training_ratio 1 and launched eagerly, the
+roofline legs, the WC sites on the GPU, cpu_baseline (--no-cpu-baseline skips it, --cpu-port adds the C-ABI port) and,
+with several ranks, the multi-GPU self-diagnosis.
+
+--dump-outputs DIR writes what the last timed step hands its caller (see dump_outputs), so that two builds can be
+compared output for output on identical, seeded inputs.
 --config picks one of BASELINE.json's GPU configurations (wc_gan_amd.train.CONFIGS); the default is the headline one.
 --dry-run is the CPU rehearsal of the N-rank path (gloo, a tiny model without HIP layers): launch, rendezvous, the
 flat gradient buckets and the place of every all-reduce -- what tests/test_bench_launch.py checks with two ranks.
@@ -59,8 +66,13 @@ def parse_args(argv=None):
                     help="which BASELINE.json configuration to step (default: the headline one)")
     ap.add_argument("--training-ratio", type=int, default=TRAINING_RATIO)
     ap.add_argument("--sync-wc", action="store_true", help="all-reduce WC statistics across replicas")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-port", action="store_true", help="also time the C-ABI CPU restatement (oracle/wc_cpu.cpp; ~45 s more)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything besides the headline figure (ratio-1 and eager steps, "
+                         "roofline legs, WC sites on the GPU, CPU baseline, multi-GPU diagnostics)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returns and updates (losses, model state) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--cpu-port", action="store_true", help="with --full: also time the C-ABI CPU restatement (oracle/wc_cpu.cpp; ~45 s more)")
     ap.add_argument("--graph", action="store_true",
                     help="replay the whole G+D step as one hipGraph.  The default on one GPU: with ~2000 launches per step the "
                          "eager loop is at the edge of host-bound; the eager step is reported next to it")
@@ -71,7 +83,10 @@ def parse_args(argv=None):
     ap.add_argument("--eager", action="store_true", help="launch kernel by kernel from Python")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the N-rank launch path: gloo backend, a tiny model without HIP layers")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port():
@@ -588,6 +603,37 @@ def multi_rank_diagnostics(trainer, eager_step, my_s_per_step, world, group, dev
                                             if b.flat is not None))}
 
 
+DUMP_BUDGET_BYTES = 60_000_000      # of array data; the .npy headers stay well inside 64 MB
+
+
+def dump_outputs(out_dir, trainer, losses):
+    """--dump-outputs: what the last timed step hands its caller -- the two losses GanTrainer.step returns and the state it updates
+    in place (every floating-point entry of the generator's and the critic's state_dict) -- as out_dir/<name>.npy: d_loss, g_loss,
+    G.<key>, D.<key>; float64 entries stay float64, everything else is written as float32.  Above DUMP_BUDGET_BYTES in all (the
+    Tiny-ImageNet critic) every array is cut to the same share of its elements, a fixed sample drawn with a seed taken from its
+    name, and written flat.  Called on rank 0 right after the timed steps, before any --full leg steps the trainer again."""
+    import zlib
+    import numpy as np
+    import torch
+    arrays = {"d_loss": losses[0], "g_loss": losses[1]}
+    for prefix, net in (("G", trainer.G), ("D", trainer.D)):
+        for key, t in net.state_dict().items():
+            if t.is_floating_point():
+                arrays[f"{prefix}.{key}"] = t
+    arrays = {name: t.detach().to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).contiguous().numpy()
+              for name, t in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    share = min(1.0, DUMP_BUDGET_BYTES / total)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if share < 1.0:
+            rng = np.random.default_rng([1234, zlib.crc32(name.encode())])
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, size=max(1, int(a.size * share)), replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"[bench] wrote {len(arrays)} arrays to {out_dir}" + (f" (a seeded sample of {share:.4f} of each)" if share < 1.0 else ""),
+          file=sys.stderr, flush=True)
+
+
 def dry_run(args, world, rank):
     """The N-rank path on the CPU: rendezvous over gloo, flat gradient buckets, GanTrainer.step with the all-reduces,
     the cut points capture_segments() would use -- with a tiny model that contains no HIP layer (batch norm + diagonal
@@ -623,11 +669,13 @@ def dry_run(args, world, rank):
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        tr.step(reals)
+        losses = tr.step(reals)
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
-    diag = multi_rank_diagnostics(tr, lambda: tr.step(reals), dt / args.steps, world, group, None, max(1, min(2, args.steps)))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, losses)
+    diag = multi_rank_diagnostics(tr, lambda: tr.step(reals), dt / args.steps, world, group, None, max(1, min(2, args.steps))) if args.full else None
     w = torch.cat([p.detach().reshape(-1) for p in list(G.parameters()) + list(D.parameters())])
     same = True
     orders = [order]
@@ -641,14 +689,16 @@ def dry_run(args, world, rank):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     if rank == 0:
-        print(json.dumps({"metric": "images/sec G+D step (dry run: tiny CPU model, not a measurement)", "dry_run": True,
-                          "value": round(4.0 * world * args.steps / dt, 2), "unit": "images/sec", "n_gpus": world,
-                          "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-                          "replicas_identical": bool(same), "allreduce_order": orders, "finite": bool(torch.isfinite(w).all()),
-                          "config": {"launch": "eager", "launch_fallback": None}, "multi_gpu": diag,
-                          # the GPU-only legs go through safe() here too: on the CPU they throw, and the line is printed all the same
-                          "roofline": safe(lambda: roofline_apply(torch.device("cpu")), "roofline_apply (dry run: expected to fail without a GPU)")}),
-              flush=True)
+        out = {"metric": "images/sec G+D step (dry run: tiny CPU model, not a measurement)", "dry_run": True,
+               "value": round(4.0 * world * args.steps / dt, 2), "unit": "images/sec", "n_gpus": world,
+               "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+               "replicas_identical": bool(same), "allreduce_order": orders, "finite": bool(torch.isfinite(w).all()),
+               "config": {"launch": "eager", "launch_fallback": None}}
+        if args.full:
+            out["multi_gpu"] = diag
+            # the GPU-only legs go through safe() here too: on the CPU they throw, and the line is printed all the same
+            out["roofline"] = safe(lambda: roofline_apply(torch.device("cpu")), "roofline_apply (dry run: expected to fail without a GPU)")
+        print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -756,7 +806,7 @@ def main(argv=None):
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        losses = step()
     barrier()
     dt = time.perf_counter() - t0
     dt_mine = dt
@@ -764,6 +814,46 @@ def main(argv=None):
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, losses)
+    extra = full_legs(args, trainer, eager_step, reals, labels, launch_mode, launch_fallback, dt_mine, world, rank, group, dev,
+                      barrier, all_ok) if args.full else {}
+    if rank == 0:
+        out = {
+            "metric": "images/sec G+D step, CIFAR-10 ResNet-SN+WC, batch 64" if args.config == "cifar10_uncond"
+                      else f"images/sec G+D step, {args.config} ResNet-SN+WC, batch 64",
+            "value": round(64.0 * world * args.steps / dt, 2), "unit": "images/sec",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{WORKLOADS[args.config]}, batch 64/GPU, training_ratio {args.training_ratio}, "
+                                   "generator_batch_multiple 2",
+                       "name": args.config, "parallelism": f"dp{world}",
+                       "wc_statistics": "sync" if args.sync_wc else "per-replica", "launch": launch_mode,
+                       "launch_fallback": launch_fallback},
+        }
+        out.update(extra)
+        # whatever the C side has buffered for stdout (RCCL's version banner when a communicator exists) goes out FIRST: the result is
+        # then the last line a reader of this process's stdout sees, not followed by C-stdio text flushed at exit
+        try:
+            import ctypes
+            sys.stdout.flush()
+            ctypes.CDLL(None).fflush(None)
+        except Exception:
+            pass
+        print(json.dumps(out), flush=True)
+    if in_group:
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
+def full_legs(args, trainer, eager_step, reals, labels, launch_mode, launch_fallback, dt_mine, world, rank, group, dev, barrier, all_ok):
+    """--full: every measurement besides the headline step, run after it (they step the trainer further) -> the keys they add to
+    rank 0's line ({} on the other ranks).  All ranks call this: the ratio-1 and eager steps and the diagnostics hold collectives."""
+    import torch
+    import torch.distributed as dist
+    in_group = group is not None
 
     # BASELINE.md: training_ratio is an upstream-recall default -> also report the step at ratio 1.  Launched the way the
     # headline step is (round 2 timed it eagerly, where it is host-bound: 3 675 images/sec on the driver's box against
@@ -816,8 +906,8 @@ def main(argv=None):
         diag = multi_rank_diagnostics(trainer, eager_step, dt_mine / args.steps, world, group, dev, 2)
         diag["launch_agreed"] = launch_mode
         diag["launch_fallback"] = launch_fallback
+    extra = {}
     if rank == 0:
-        extra = {}
         if diag is not None:
             extra["multi_gpu"] = diag
         if dt_eager is not None:
@@ -825,8 +915,8 @@ def main(argv=None):
         if dt1 is not None:
             extra["training_ratio_1"] = {"value": round(64.0 * world / dt1, 2), "unit": "images/sec", "ms_per_step": round(dt1 * 1e3, 3),
                                          "launch": launch1}
-        roof = safe(lambda: roofline_apply(dev), "roofline_apply")
-        cpu = None
+        extra["roofline"] = safe(lambda: roofline_apply(dev), "roofline_apply")
+        extra["cpu_baseline"] = None
         if world == 1:
             sites = site_list(args.config)
             extra["roofline_conv"] = safe(lambda: conv_roofline(dev), "conv_roofline")
@@ -835,40 +925,13 @@ def main(argv=None):
                 return {"value": round(64.0 / wc_gpu, 1), "unit": "images/sec (WC sites of one G+D step only)", "ms": round(wc_gpu * 1e3, 3)}
             extra["wc_sites_gpu"] = safe(_wc_gpu, "wc_sites_gpu")
             if not args.no_cpu_baseline:
-                cpu = safe(lambda: cpu_baseline(args.training_ratio, sites, args.config), "cpu_baseline")
+                extra["cpu_baseline"] = safe(lambda: cpu_baseline(args.training_ratio, sites, args.config), "cpu_baseline")
                 if args.cpu_port:         # the C-ABI CPU restatement, 4.5 x slower than the torch-CPU leg and ~45 s of wall time: on request
                     try:
                         extra["cpu_port"] = cpu_port_baseline(args.training_ratio, sites, args.config)
                     except Exception as ex:                       # the port is test infrastructure: its absence is not an error of the bench
                         extra["cpu_port"] = {"value": None, "kind": "port", "error": repr(ex)[:200]}
-        out = {
-            "metric": "images/sec G+D step, CIFAR-10 ResNet-SN+WC, batch 64" if args.config == "cifar10_uncond"
-                      else f"images/sec G+D step, {args.config} ResNet-SN+WC, batch 64",
-            "value": round(64.0 * world * args.steps / dt, 2), "unit": "images/sec",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{WORKLOADS[args.config]}, batch 64/GPU, training_ratio {args.training_ratio}, "
-                                   "generator_batch_multiple 2",
-                       "name": args.config, "parallelism": f"dp{world}",
-                       "wc_statistics": "sync" if args.sync_wc else "per-replica", "launch": launch_mode,
-                       "launch_fallback": launch_fallback},
-            "roofline": roof, "cpu_baseline": cpu,
-        }
-        out.update(extra)
-        # whatever the C side has buffered for stdout (RCCL's version banner when a communicator exists) goes out FIRST: the result is
-        # then the last line a reader of this process's stdout sees, not followed by C-stdio text flushed at exit
-        try:
-            import ctypes
-            sys.stdout.flush()
-            ctypes.CDLL(None).fflush(None)
-        except Exception:
-            pass
-        print(json.dumps(out), flush=True)
-    if in_group:
-        dist.barrier()
-        dist.destroy_process_group()
-    return 0
+    return extra
 
 
 if __name__ == "__main__":

@@ -1,5 +1,6 @@
-"""The bench line's contract on a GPU: `python bench.py` (short run, no CPU baseline) prints ONE JSON line with the driver's keys, the
-roofline object of the dominant kernel and a self-consistent achieved / frac."""
+"""The bench line's contract on a GPU: `python bench.py --full` (short run, no CPU baseline) prints ONE JSON line with the driver's keys,
+the roofline object of the dominant kernel and a self-consistent achieved / frac; a plain run prints the headline keys alone and writes
+what its last step computed under --dump-outputs."""
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_line_contract():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -35,6 +36,27 @@ def test_bench_line_contract():
     assert abs(r_["frac"] - r_["achieved"] / r_["peak"]) < 1e-3
     assert 0.3 < r_["frac_of_loop_copy"] <= r_["frac_of_isolated_copy"] * 1.05 < 1.05 and "error" not in r_
     assert r_["traffic"] is None or 0.9 < r_["traffic"] / r_["algorithmic_bytes"] < 1.5
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    import numpy as np
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path)],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["dtype"] == "f32" and abs(d["value"] * d["ms_per_step"] / 1e3 - 64.0) < 0.5
+    assert not {"roofline", "cpu_baseline", "eager_launch", "training_ratio_1", "roofline_conv", "wc_sites_gpu", "multi_gpu"} & set(d)
+    names = {f[:-4] for f in os.listdir(tmp_path)}
+    assert {"d_loss", "g_loss", "G.dense.weight", "D.out.weight"} <= names
+    total = 0
+    for n in names:
+        a = np.load(tmp_path / (n + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+        total += a.nbytes
+    assert total <= 64e6
 
 
 def test_roofline_names_a_kernel_that_the_generator_step_launches():

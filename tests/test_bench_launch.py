@@ -27,7 +27,7 @@ def _json_line(stdout):
 
 
 def test_gpus_2_spawns_two_ranks_and_keeps_replicas_consistent():
-    r = _run(["--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "1", "--training-ratio", "2"])
+    r = _run(["--gpus", "2", "--dry-run", "--full", "--steps", "2", "--warmup", "1", "--training-ratio", "2"])
     assert r.returncode == 0, r.stderr[-2000:]
     out = _json_line(r.stdout)
     assert out["dry_run"] is True and out["n_gpus"] == 2 and out["steps"] == 2
@@ -51,6 +51,24 @@ def test_single_rank_dry_run_needs_no_process_group():
     assert r.returncode == 0, r.stderr[-2000:]
     out = _json_line(r.stdout)
     assert out["n_gpus"] == 1 and out["allreduce_order"] == [["d", "g"]]
+
+
+def test_dump_outputs_repeat_from_run_to_run(tmp_path):
+    """--dump-outputs writes the last timed step's losses and model state as float32 .npy files, from inputs that are the same
+    in every run with the same arguments; a plain run carries none of the --full legs."""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        r = _run(["--dry-run", "--steps", "2", "--warmup", "1", "--training-ratio", "2", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = _json_line(r.stdout)
+        assert "roofline" not in out and "multi_gpu" not in out
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and {"d_loss.npy", "g_loss.npy"} <= set(names)
+    assert any(n.startswith("G.") for n in names) and any(n.startswith("D.") for n in names)
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
 
 
 def test_world_size_that_contradicts_gpus_is_refused():

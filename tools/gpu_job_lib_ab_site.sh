@@ -4,7 +4,7 @@ N=$1; shift
 for r in $(seq 1 $N); do
   for V in main "$@"; do
     L=$R/wc_gan_amd/libwc_hip.so; [ $V != main ] && L=$R/wc_gan_amd/csrc/build/var/lib_$V.so
-    python tools/bench_with_lib.py $L --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+    python tools/bench_with_lib.py $L --steps 20 --warmup 5 --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -22,6 +22,6 @@ for mode in "new miopen".split():
         d = sorted(d)
         print(f"{mode:6s} {k:110s} n={len(d):3d} min {d[0]:7.1f} med {d[len(d)//2]:7.1f} max {d[-1]:7.1f}")
 PY
-for V in 0 1; do WC_NARROW_WRW=$V timeout 500 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+for V in 0 1; do WC_NARROW_WRW=$V timeout 500 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('narrow_wrw=$V', d['value'], d['ms_per_step'], r.get('launch_us'), r.get('error'))"; done >> gpurun_out/r5g_summary.txt 2>&1

@@ -25,7 +25,7 @@ for mode in "rs0 rs1".split():
         print(f"{mode:6s} {k:90s} n={len(d):3d} min {d[0]:7.1f} med {d[len(d)//2]:7.1f} avg {sum(d)/len(d):7.1f} max {d[-1]:7.1f}")
     print(f"{mode:6s} sum of medians per call: {tot:.1f} us")
 PY
-for V in 0 1 0 1; do WC_RX_SAMPLE_KERNEL=$V timeout 500 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+for V in 0 1 0 1; do WC_RX_SAMPLE_KERNEL=$V timeout 500 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('sample_kernel=$V', d['value'], d['ms_per_step'], r.get('forward_site_us'), r.get('producer_us'), r.get('forward_site_plus_producer_us'), r.get('launch_us'), r.get('error'))"; done >> gpurun_out/r5c_summary.txt 2>&1
 tail -12 gpurun_out/r5c_producer.txt; cat gpurun_out/r5c_summary.txt
