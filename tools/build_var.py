@@ -1,5 +1,5 @@
 """Development: variants of ONE source of libwc_hip.so -> wc_gan_amd/csrc/build/var/lib_<tag>.so (the other objects are the in-tree build's).
-usage: tools/build_var.py wc_split base= STAMPS=-DWC_SPLIT_STAMPS=1 ...      (tag=flags; flags may be empty)"""
+usage: tools/build_var.py wc_split base= o2=-O2 ...      (tag=flags; flags may be empty)"""
 import glob, os, subprocess, sys
 from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

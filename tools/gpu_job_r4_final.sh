@@ -16,10 +16,8 @@ cd $R
 python tools/site_timeline_print.py gpurun_out/r4z_site_tl/s_kernel_trace.csv resadd_sample > gpurun_out/r4z_site_timeline.txt 2>&1
 python tools/k6_spread.py 2>&1 | grep -v amdgpu.ids > gpurun_out/r4z_k6_spread.txt
 python tools/k3_zero_planes.py 2>&1 | grep -v amdgpu.ids > gpurun_out/r4z_k3_zero_planes.txt
-# K2: every wave's barrier arrivals / departures (a -DCF_STAMPS=1 build of wc_small.hip made beforehand: tools/build_var.py wc_small st=-DCF_STAMPS=1) and the per-call times
-[ -f wc_gan_amd/csrc/build/var/lib_st.so ] && python tools/k2_stamps.py 256 wc_gan_amd/csrc/build/var/lib_st.so 2>&1 | grep -v amdgpu.ids > gpurun_out/r4z_k2_stamps.txt
+# K2: the per-call times
 python tools/k2_pipe_check.py 10 2>&1 | grep -v amdgpu.ids > gpurun_out/r4z_k2_pipe_check.txt
-python tools/k6_variants.py 2>&1 | grep -v amdgpu.ids > gpurun_out/r4z_k6_variants.txt
 for CFG in cifar10_cond stl10_uncond tinyimagenet_cond_sa; do
   timeout 600 python bench.py --config $CFG --steps 8 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys

@@ -8,5 +8,4 @@ python tools/seed_sweep.py 5 --ref32 2>&1 | grep -v amdgpu.ids > gpurun_out/r4_s
 python tools/seed_sweep.py 3 --planes 2>&1 | grep -v amdgpu.ids > gpurun_out/r4_seed_sweep_base_planes.txt
 python tools/seed_sweep.py 3 --families --ref32 2>&1 | grep -v amdgpu.ids > gpurun_out/r4_seed_sweep_families.txt
 python tools/seed_sweep.py 2 --families --planes 2>&1 | grep -v amdgpu.ids > gpurun_out/r4_seed_sweep_families_planes.txt
-WC_K1_NO_BIAS_COMP=1 python tools/seed_sweep.py 2 --families 2>&1 | grep -v amdgpu.ids > gpurun_out/r4_seed_sweep_families_nocomp.txt
 grep -h "WORST\|worst\|cond of\|REF32" gpurun_out/r4_seed_sweep_*.txt

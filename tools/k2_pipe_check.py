@@ -1,6 +1,6 @@
 """K2 with the inverse inside the factor launch (tri_inverse_role): W L = I and L L^T = T residuals in float64 for several
 widths / group counts, repeated (the hand-off is a race if it is wrong), and the time per call.  Run once per mode:
-default (one launch), WC_K2_SPLIT=1 (the four-waves-per-column inverse as its own launch), WC_K2_TWO_LAUNCH=1 (round-2a kernels)."""
+default (one launch) and WC_K2_TWO_LAUNCH=1 (round-2a kernels)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from wc_gan_amd import _lib

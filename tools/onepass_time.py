@@ -13,4 +13,4 @@ def t(fn, it=20):
     for _ in range(it): fn()
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / it * 1e3
-print("K6 with scales (one pass unless WC_K6_TWO_PASS): %.1f us" % t(lambda: ops.bwd_apply(gy, x, mu, At, S, gm, None, scales=scales)))
+print("K6 with scales (one pass): %.1f us" % t(lambda: ops.bwd_apply(gy, x, mu, At, S, gm, None, scales=scales)))

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <mutex>
 
 typedef float  f32x4  __attribute__((ext_vector_type(4)));
 
@@ -62,6 +63,30 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 #define WC_WAVE 64
 
 static inline size_t wc_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) for a launch of `kernel` with `bytes` of dynamic LDS on the current device.
+// The call is not free on the host, so the largest value set is remembered per (kernel, device) and the attribute is set
+// again only when a launch needs more.  (A full table only loses the caching.)
+inline hipError_t wc_set_max_lds(const void* kernel, size_t bytes)
+{
+    struct Entry { const void* kernel; int device; size_t bytes; };
+    static Entry table[256];
+    static int used = 0;
+    static std::mutex mu;
+    int device = 0;
+    hipError_t e = hipGetDevice(&device);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lock(mu);
+    Entry* hit = nullptr;
+    for (int i = 0; i < used && !hit; ++i)
+        if (table[i].kernel == kernel && table[i].device == device) hit = &table[i];
+    if (hit && hit->bytes >= bytes) return hipSuccess;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return e;
+    if (!hit && used < 256) { hit = &table[used++]; hit->kernel = kernel; hit->device = device; }
+    if (hit) hit->bytes = bytes;
+    return hipSuccess;
+}
 
 // ----- big-tensor kernels (wc_rows.hip) ------------------------------------------------------
 

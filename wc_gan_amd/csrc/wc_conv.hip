@@ -18,7 +18,7 @@
 //   * a workgroup = 4 waves as 2x2, each wave (32 MB) pixels x (32 NB) outputs with 16 MB NB accumulator registers; one
 //     iteration = (tap, 32 input channels) = 2 k-steps; two LDS stages, one barrier per iteration, hand-placed: fragments
 //     of k-step 0 right behind the barrier, then the MFMAs with the next iteration's addresses, DMAs and the fragment
-//     reads of k-step 1 in their shadow (WC_CONV_PIPE).
+//     reads of k-step 1 in their shadow.
 //   * small grids (< ~100 workgroups) share the (tap, chunk) loop over blockIdx.z (conv_ksplit_reduce_kernel finishes).
 //   * weight gradient: conv_wrw_kernel (pixel-major tiles, ds_read_b64_tr_b16 fragments, split over pixel ranges) +
 //     conv_wrw_reduce_kernel (fixed-order sum into the weight's layout, 4x4 slices folded back onto 3x3 taps).
@@ -27,9 +27,6 @@
 #include "../../include/wc_hip.h"
 #include <stdlib.h>
 
-#ifndef WC_CONV_PIPE
-#define WC_CONV_PIPE 1   // 0: the compiler-scheduled k-loop (development)
-#endif
 
 namespace {
 
@@ -123,7 +120,6 @@ __global__ __launch_bounds__(256) void conv_f16x3_kernel(ConvArgs a)
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
     const int it0 = KS ? (int)blockIdx.z * iters / a.ksplit : 0, it1 = KS ? ((int)blockIdx.z + 1) * iters / a.ksplit : iters;
-#if WC_CONV_PIPE
     // Hand-placed iteration: the fragments of k-step 0 right behind the barrier, then the MFMAs of both k-steps with the
     // next iteration's DMAs (one every GAP MFMAs) and the fragment reads of k-step 1 in their shadow -- the wave issues
     // in order, so whatever stands between the barrier and the first MFMA is time the MFMA pipe idles.
@@ -207,46 +203,6 @@ __global__ __launch_bounds__(256) void conv_f16x3_kernel(ConvArgs a)
         }
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);            // the idle stage's last DMAs
-#else
-    issue(it0, 0);
-    for (int it = it0; it < it1; ++it) {
-        const int stage = (it - it0) & 1;
-        __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0): this wave's chunks of the stage have landed
-        __syncthreads();                           // ... and everybody's; the other stage is free (its readers are done)
-        if (it + 1 < it1) issue(it + 1, stage ^ 1);
-        const char* sa = smem + stage * STAGE;
-        const char* sb = sa + A_BYTES;
-        #pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            f16x8 ah[MB], al[MB], bh[NB], bl[NB];
-            #pragma unroll
-            for (int i = 0; i < MB; ++i) {
-                const char* p = sa + (((wm * MB + i) * 2 + s) * 2) * 1024 + lane * 16;
-                ah[i] = *reinterpret_cast<const f16x8*>(p);
-                al[i] = *reinterpret_cast<const f16x8*>(p + 1024);
-            }
-            #pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                const char* p = sb + (((wn * NB + j) * 2 + s) * 2) * 1024 + lane * 16;
-                bh[j] = *reinterpret_cast<const f16x8*>(p);
-                bl[j] = *reinterpret_cast<const f16x8*>(p + 1024);
-            }
-            #pragma unroll
-            for (int i = 0; i < MB; ++i)
-                #pragma unroll
-                for (int j = 0; j < NB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-            #pragma unroll
-            for (int i = 0; i < MB; ++i)
-                #pragma unroll
-                for (int j = 0; j < NB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-            #pragma unroll
-            for (int i = 0; i < MB; ++i)
-                #pragma unroll
-                for (int j = 0; j < NB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
-    }
-
-#endif
     // epilogue: unscale, bias, scatter rows to their output pixels
     const float inv = 1.0f / (a.xscale[0] * a.wscale[0]);
     const int oy0 = a.offy[phase], ox0 = a.offx[phase];
@@ -725,7 +681,6 @@ __global__ __launch_bounds__(256) void conv_wrw_kernel(WrwArgs a)
     // transposing-read address of this lane inside a 1-KiB (16 pixels x 64 B) block
     const int tr_off = ((lane >> 5) * 8 + ((lane & 15) >> 2)) * 64 + (((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2;
 
-#if WC_CONV_PIPE
     // the hand-placed iteration of conv_f16x3_kernel: fragments of k-step 0 behind the barrier, the next chunk's
     // addresses and DMAs and the transposing reads of k-step 1 in the shadow of the MFMAs
     constexpr int NA = AQ * 4, ND = NA + BQ * 4, HALF = ND / 2, PER = 3 * MB * NB, GAP = PER / HALF;
@@ -810,46 +765,6 @@ __global__ __launch_bounds__(256) void conv_wrw_kernel(WrwArgs a)
         }
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);
-#else
-    if (c0 < c1) issue(c0, 0);
-    for (int c = c0; c < c1; ++c) {
-        const int stage = (c - c0) & 1;
-        __builtin_amdgcn_s_waitcnt(0x0F70);
-        __syncthreads();
-        if (c + 1 < c1) issue(c + 1, stage ^ 1);
-        const char* sa = smem + stage * STAGE;
-        const char* sb = sa + A_BYTES;
-        #pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            f16x8 ah[MB], al[MB], bh[NB], bl[NB];
-            #pragma unroll
-            for (int i = 0; i < MB; ++i) {
-                const char* p = sa + (((wm * MB + i) * 2 + s) * 2) * 1024;
-                ah[i] = tr_read8(p, tr_off);
-                al[i] = tr_read8(p + 1024, tr_off);
-            }
-            #pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                const char* p = sb + (((wn * NB + j) * 2 + s) * 2) * 1024;
-                bh[j] = tr_read8(p, tr_off);
-                bl[j] = tr_read8(p + 1024, tr_off);
-            }
-            #pragma unroll
-            for (int i = 0; i < MB; ++i)
-                #pragma unroll
-                for (int j = 0; j < NB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-            #pragma unroll
-            for (int i = 0; i < MB; ++i)
-                #pragma unroll
-                for (int j = 0; j < NB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-            #pragma unroll
-            for (int i = 0; i < MB; ++i)
-                #pragma unroll
-                for (int j = 0; j < NB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
-    }
-
-#endif
 
     const int slice = phase * a.ntaps + tap, nslice = a.nphase * a.ntaps;
     float* out = a.partial + ((int64_t)blockIdx.x * nslice + slice) * a.A.C * a.B.C;
@@ -1047,9 +962,6 @@ struct NarrowFwdArgs {
     signed char tdy[32], tdx[32], tch[32], tr[32], ts[32];     // row m of A: tap offsets, input channel, the weight's tap indices (host-made: no divisions on the device)
 };
 
-#ifndef WC_NF_ABL
-#define WC_NF_ABL 0      // development (timing only, wrong results): 1 no global stores, 2 no gathers, 4 no MFMAs, 8 no LDS transpose
-#endif
 constexpr int kNarrowLd = 32 * 2 + 4;     // floats per pixel row of a wave's LDS tile (16-byte aligned, the two lane halves 16 banks apart)
 constexpr int kNarrowNQ = 2;          // 32-channel output blocks per wave: 64 channels (4 blocks took 316 registers: one wave per SIMD, 35 us)
 template <int KS>
@@ -1105,7 +1017,7 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_narrow_kernel(NarrowFwdArgs a
         for (int s = 0; s < KS; ++s) {
             const int dy = (signed char)(dyx[s] & 0xff), dx = (signed char)((dyx[s] >> 8) & 0xff), kind = dyx[s] >> 16;
             const bool inb = kind == 0 && (unsigned)((int)yy + dy) < (unsigned)a.H && (unsigned)((int)xx + dx) < (unsigned)a.W;
-            const float xv = (WC_NF_ABL & 2) ? 1.f : a.x[inb ? pb + off[s] : 0];
+            const float xv = a.x[inb ? pb + off[s] : 0];
             av[s] = inb ? xv : (kind == 1 ? 1.f : 0.f);
         }
     };
@@ -1121,7 +1033,7 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_narrow_kernel(NarrowFwdArgs a
 #pragma unroll
         for (int s = 0; s < KS; ++s)
 #pragma unroll
-            for (int q = 0; q < kNarrowNQ; ++q) { if (WC_NF_ABL & 4) acc[q][s & 15] += av[s] * bw[s][q]; else acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bw[s][q], acc[q], 0, 0, 0); }
+            for (int q = 0; q < kNarrowNQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bw[s][q], acc[q], 0, 0, 0);
         // rows = pixels (r & 3) + 8 (r >> 2) + 4 k of the tile, columns = output channel q * 32 + i of the group: through LDS, so that the
         // tile leaves as 16 bytes per lane, four whole 256-byte pixel rows per store (4 bytes per lane in 128-byte pieces ran at 2.6 TB/s)
         float* tl = nf_tile + wave * (32 * kNarrowLd);
@@ -1141,7 +1053,7 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_narrow_kernel(NarrowFwdArgs a
             const int row = 4 * j + (lane >> 4);
             const int64_t pr = (int64_t)t * 32 + row;
             const f32x4 v = *reinterpret_cast<const f32x4*>(tl + row * kNarrowLd + 4 * (lane & 15));
-            if (pr < a.M && (!(WC_NF_ABL & 1) || v[0] == 1.2345f)) *reinterpret_cast<f32x4*>(a.y + pr * a.Cout + grp * (32 * kNarrowNQ) + 4 * (lane & 15)) = v;
+            if (pr < a.M) *reinterpret_cast<f32x4*>(a.y + pr * a.Cout + grp * (32 * kNarrowNQ) + 4 * (lane & 15)) = v;
         }
 #pragma unroll
         for (int s = 0; s < KS; ++s) av[s] = an[s];
@@ -1168,13 +1080,8 @@ template <int MB, int NB, bool KS = false>
 hipError_t launch_conv(const ConvArgs& a, hipStream_t st)
 {
     constexpr int LDS = 2 * (2 * MB * 4 * 1024 + 2 * NB * 4 * 1024);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_f16x3_kernel<MB, NB, KS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(conv_f16x3_kernel<MB, NB, KS>), LDS);
+    if (e != hipSuccess) return e;
     const int64_t M = (int64_t)a.N * a.H * a.W;
     dim3 grid((unsigned)(M / (64 * MB)), (unsigned)(a.nphase * (a.Cout / (64 * NB))), (unsigned)a.ksplit);
     hipLaunchKernelGGL((conv_f16x3_kernel<MB, NB, KS>), grid, dim3(256), LDS, st, a);
@@ -1310,6 +1217,10 @@ int wc_conv_supported(const wc_conv_geom* g)
     return 1;
 }
 
+constexpr int kKsplitMaxWgs = 96;         // k-split only grids of at most this many output tiles ...
+constexpr int kKsplitTargetWgs = 256;     // ... into about this many workgroups
+constexpr int kWrwTargetWgs = 512;        // weight gradient: workgroups over all tiles and pixel ranges
+
 static int conv_ksplit(const wc_conv_geom* g)
 {
     // small grids leave most CUs idle with 128-point x (128|256)-output tiles: share the (tap, chunk) loop
@@ -1317,10 +1228,8 @@ static int conv_ksplit(const wc_conv_geom* g)
     const bool wide = (g->Cout % 256) == 0;
     const int64_t wgs = (M / 128) * g->nphase * (g->Cout / (wide ? 256 : 128));
     const int iters = g->ntaps * (g->Cin / 32);
-    static const int thr = getenv("WC_KSPLIT_WGS") ? atoi(getenv("WC_KSPLIT_WGS")) : 96;         // development knobs
-    static const int tgt = getenv("WC_KSPLIT_TARGET") ? atoi(getenv("WC_KSPLIT_TARGET")) : 256;
-    if (wgs > thr || iters < 8) return 1;
-    int k = (int)((tgt + wgs - 1) / wgs);
+    if (wgs > kKsplitMaxWgs || iters < 8) return 1;
+    int k = (int)((kKsplitTargetWgs + wgs - 1) / wgs);
     if (k > iters / 4) k = iters / 4;               // at least 4 iterations each
     return k < 1 ? 1 : (k > 8 ? 8 : k);
 }
@@ -1380,8 +1289,7 @@ static int wrw_splits(const wc_conv_geom* g, int* tile)
     // The workgroups of one pixel range (one per slice and tile) read the same activations: a split count that is a
     // multiple of 8 puts them on one XCD (workgroup id mod 8), i.e. behind one L2 -- measured 650 against 790 us at
     // 128 x 32 x 32 x 256 x 256 for 56 against 28 ranges.  About two workgroups per CU in all.
-    static const int target = getenv("WC_WRW_TARGET") ? atoi(getenv("WC_WRW_TARGET")) : 512;      // development knob
-    int splits = target / tiles / 8 * 8;
+    int splits = kWrwTargetWgs / tiles / 8 * 8;
     if (splits < 8) splits = 8;
     if (splits > 64) splits = 64;                   // (the partial sums are splits x the weight size)
     if (splits > nchunks) splits = (int)nchunks;
@@ -1461,12 +1369,8 @@ int wc_conv_wrw_narrow_f32(const float* x, const float* gy, int64_t N, int64_t H
     a.M = N * H * W;
     const int nparts = (int)narrow_wrw_parts(a.M, &a.pix_per_wave);
     constexpr int lds = 8 * 4096 * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wrw_narrow_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(conv_wrw_narrow_kernel), lds);
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(conv_wrw_narrow_kernel, dim3(nparts, Cout / 128), dim3(512), lds, st, a);
     hipLaunchKernelGGL(conv_wrw_narrow_reduce_kernel, dim3(128, Cout / 128), dim3(256), 0, st, (const float*)ws, nparts, Cin, ksize, a.nrow,
                        dw, stride_k, stride_n, stride_r, stride_s, db);
@@ -1526,8 +1430,7 @@ int wc_conv_wrw_bias_f16x3(const void* xhi, const void* xlo, const float* xscale
             }
         }
     // the lanes of a result tile run along its columns: put the weight's contiguous channel axis there
-    static const bool noswap = getenv("WC_WRW_NOSWAP") != nullptr;                              // development knob
-    const bool x_cols = stride_k == 1 && !noswap;
+    const bool x_cols = stride_k == 1;
     WrwArgs a;
     a.A = x_cols ? G : X; a.B = x_cols ? X : G;
     a.zero = (const _Float16*)zero_line; a.partial = (float*)ws;
@@ -1540,13 +1443,13 @@ int wc_conv_wrw_bias_f16x3(const void* xhi, const void* xlo, const float* xscale
     hipError_t e = hipSuccess;
     if (T == 256) {
         constexpr int LDS = 2 * (2 * 4 * 4 * 1024 + 2 * 4 * 4 * 1024);
-        static bool set = false;
-        if (!set) { e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wrw_kernel<4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS); if (e != hipSuccess) return (int)e; set = true; }
+        e = wc_set_max_lds(reinterpret_cast<const void*>(conv_wrw_kernel<4, 4>), LDS);
+        if (e != hipSuccess) return (int)e;
         hipLaunchKernelGGL((conv_wrw_kernel<4, 4>), grid, dim3(256), LDS, st, a);
     } else {
         constexpr int LDS = 2 * (2 * 2 * 4 * 1024 + 2 * 2 * 4 * 1024);
-        static bool set = false;
-        if (!set) { e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wrw_kernel<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS); if (e != hipSuccess) return (int)e; set = true; }
+        e = wc_set_max_lds(reinterpret_cast<const void*>(conv_wrw_kernel<2, 2>), LDS);
+        if (e != hipSuccess) return (int)e;
         hipLaunchKernelGGL((conv_wrw_kernel<2, 2>), grid, dim3(256), LDS, st, a);
     }
     r.partial = (const float*)ws; r.splits = splits; r.nslice = nslice; r.Ca = a.A.C; r.Cb = a.B.C;

@@ -18,40 +18,7 @@
 // Tiles are double-buffered; the loads of tile t+2 are in flight while tile t is on the matrix pipe.
 #include "wc_common.h"
 #include <stdlib.h>
-#ifndef WC_MFMA16
-#define WC_MFMA16 1     // ring kernel on v_mfma_f32_16x16x32_f16 and the fp16 tables in that shape's load order (0: 32x32x16, development)
-#endif
-#ifndef WC_NT_STORE
-#define WC_NT_STORE 1      // nontemporal stores of y in the ring kernel's epilogue (y is streamed out: K3 53.5 -> 50.1 us, the step unchanged)
-#endif
-#ifndef WC_NT_STORE_K6
-#define WC_NT_STORE_K6 0   // the same for dx in the one-pass K6 kernel: measured (stage 138 -> 133.5 us in bench.py's loop, nothing under rocprofv3) and left off -- its stores are 64-byte pieces of a row, which leave the chip un-merged: HBM writes 134 -> 164 MB per launch (WRITE_SIZE), the step unchanged
-#endif
-#ifndef WC_FENCE_DEP
-#define WC_FENCE_DEP 0     // the slot-read fence: 0 an explicit lgkmcnt(0), 1 a register dependency (measured the same)
-#endif
-#ifndef WC_M16_ORDER
-#define WC_M16_ORDER 0
-#endif
-#ifndef WC_CONV_NUM
-#define WC_CONV_NUM 2      // quarters of a tile's MFMA loop that carry the next tile's conversion (3: measured the same)
-#endif
-#ifndef WC_STAMPS
-#define WC_STAMPS 0
-#endif
-#define WC_STAMP(i) do { if (WC_STAMPS && stamp_on) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); ts[i] = t_; } } while (0)
-#ifndef WC_NO_PIPE
-#ifndef WC_NT_STORE_PL
-#define WC_NT_STORE_PL 0   // planes form of the ring kernel: nontemporal stores of its 64-byte pieces (a wave owns 32 columns = 64 bytes of an fp16 row).  Measured and left off: they leave the chip un-merged -- HBM writes 170 MB per launch for 138 MB of planes + mask (WRITE_SIZE), 61 us against the fp32 form's 50, 80 us in the layer's flow; plain stores let the L2 put the two halves of a line together
-#endif
-#define WC_NO_PIPE 0   // development: 1 leaves the ring kernel's k-loop to hipcc's own schedule
-#endif
-#ifndef WC_K6_ABL
-#define WC_K6_ABL 0   // development, one-pass K6 only (results wrong; tools/k6_variants.py): 1 no dx stores, 2 no MFMA, 4 no fragment reads (with 2), 8 no conversion arithmetic / image writes, 32 no waits for the DMAs, 64 no hand-off waits (counters), 256 no DMAs of x (half of the kernel's LDS-DMA instructions)
-#endif
-#ifndef WC_ABL
-#define WC_ABL 0      // development ablation bits: 1 no stores, 2 no MFMA, 4 no staging writes, 8 no loads, 16 no counters, 32 MFMA operands from registers only
-#endif
+constexpr int WC_CONV_NUM = 2;      // quarters of a tile's MFMA loop that carry the next tile's conversion (3: measured the same)
 #include <type_traits>
 
 namespace {
@@ -191,16 +158,10 @@ __global__ __launch_bounds__(64) void split_table_kernel(SplitJob j0, SplitJob j
             // "register image" order: the 16 bytes a lane loads for MFMA fragment (column group n/32, k-step k/16) sit
             // with the other 63 lanes' in one contiguous KiB
             const int n = (int)(row % C);
-#if WC_MFMA16
             // 16x16x32 fragments: (column group n/32, k-step k/32, column half (n/16)&1): lane = 16*((k/8)&3) + n%16
             const int KS32 = C / 32;
             const int64_t idx = (row / C) * (int64_t)C * C +
                                 (((((int64_t)(n >> 5) * KS32 + (k >> 5)) * 2 + ((n >> 4) & 1)) * 64 + ((k >> 3) & 3) * 16 + (n & 15)) * 8 + (k & 7));
-#else
-            const int KS = C / 16;
-            const int64_t idx = (row / C) * (int64_t)C * C +
-                                ((((int64_t)(n >> 5) * KS + (k >> 4)) * 64 + ((k >> 3) & 1) * 32 + (n & 31)) * 8 + (k & 7));
-#endif
             hi[idx] = h;
             lo[idx] = l;
         }
@@ -228,7 +189,7 @@ struct FastArgs {
     // fp16, in which case the whole pass is redone with the scale the maximum asks for.
     _Float16* phi; _Float16* plo; float* oscale; float* oamax; const float* gate; int ngate;
     int ntiles, tiles_per_wg;
-    unsigned long long* dbg;      // WC_STAMPS builds only: s_memtime stamps of one steady-state tile
+    unsigned long long* dbg;      // (unused: where development builds put their s_memtime stamps)
 };
 
 // M must be a multiple of the row tile (the caller checks): every load and store below is unconditional, which is
@@ -336,7 +297,6 @@ __global__ __launch_bounds__(512, 2) void affine_f16x3_kernel(FastArgs a)
     int cur_slot = -1;
     const int col = cg * 32 + l31;
     auto load_b = [&](int slot) {
-#if WC_MFMA16
         // the tables are stored for the ring kernel's 16x16x32 fragments; this kernel's 32x32x16 fragment (k-step s, 8 k
         // per lane) is the same 16 bytes at: unit (s/2, column half l31/16), lane 16*(2*(s&1) + lh) + l31%16
         const int64_t lo16 = (((int64_t)cg * (KS / 2) * 2 + (l31 >> 4)) * 64 + lh * 16 + (l31 & 15)) * 8;
@@ -347,15 +307,6 @@ __global__ __launch_bounds__(512, 2) void affine_f16x3_kernel(FastArgs a)
             bhi[s] = *reinterpret_cast<const f16x8*>(ph + 1024 * (s >> 1) + 256 * (s & 1));
             blo[s] = *reinterpret_cast<const f16x8*>(pl + 1024 * (s >> 1) + 256 * (s & 1));
         }
-#else
-        const _Float16* ph = a.Bhi + (int64_t)slot * a.slot_stride + ((int64_t)cg * KS * 64 + lane) * 8;
-        const _Float16* pl = a.Blo + (int64_t)slot * a.slot_stride + ((int64_t)cg * KS * 64 + lane) * 8;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            bhi[s] = *reinterpret_cast<const f16x8*>(ph + 512 * s);
-            blo[s] = *reinterpret_cast<const f16x8*>(pl + 512 * s);
-        }
-#endif
         const int64_t srow_ = a.slot_stride ? slot : 0;
         cscale = a.colscale[srow_ * C + col];
         addv = 0.f;
@@ -379,8 +330,6 @@ __global__ __launch_bounds__(512, 2) void affine_f16x3_kernel(FastArgs a)
     const int out_lane = (4 * lh) * C + col;
     const int rd_lane = l31 * (C * 2);
 
-    unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    bool stamp_on = false;
     using T_ = std::integral_constant<bool, true>;
     using F_ = std::integral_constant<bool, false>;
     const int chunk_sb = (__builtin_amdgcn_readfirstlane(wave) >= 4) ? 1 : 0;      // wave-uniform (SGPR)
@@ -391,8 +340,6 @@ __global__ __launch_bounds__(512, 2) void affine_f16x3_kernel(FastArgs a)
     auto tile_body = [&](int t, auto do_write, auto do_load) {
         const int cur = (t - t_begin) & 1;
         constexpr bool W_ = decltype(do_write)::value, L_ = decltype(do_load)::value;
-        stamp_on = WC_STAMPS && (t == t_begin + 3);
-        WC_STAMP(0);
         if (ASM_LOADS && t == t_begin)       // the prologue's loads have no stores behind them: drain once, counts hold after
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(xr[0]), "+v"(xr[1]), "+v"(xr[2]), "+v"(xr[3]),
                                                 "+v"(xr[4]), "+v"(xr[5]), "+v"(xr[6]), "+v"(xr[7]) :: "memory");
@@ -438,23 +385,19 @@ __global__ __launch_bounds__(512, 2) void affine_f16x3_kernel(FastArgs a)
 #pragma unroll
                     for (int q = 0; q < PER; ++q) {
                         const int p = (s / STEP) * PER + q;
-                        if (W_ && ASM_LOADS && !(WC_ABL & 8)) {
+                        if (W_ && ASM_LOADS) {
                             if (L_) asm volatile("s_waitcnt vmcnt(39)" : "+v"(xr[p]) :: "memory");
                             else asm volatile("s_waitcnt vmcnt(16)" : "+v"(xr[p]) :: "memory");   // <= every tail count
                         }
-                        if (W_ && !(WC_ABL & 4)) write_chunk(cur ^ 1, p, t + 2);
-                        if (L_ && !(WC_ABL & 8)) load_chunk(t + 2, p);
+                        if (W_) write_chunk(cur ^ 1, p, t + 2);
+                        if (L_) load_chunk(t + 2, p);
                     }
                 }
-                if (WC_ABL & 2) { asm volatile("" :: "v"(ah), "v"(al)); }
-                else {
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bhi[s], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, blo[s], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bhi[s], acc, 0, 0, 0);
-                }
                 ah = nh; al = nl;
             }
-            WC_STAMP(1 + 2 * sb);
             float* po = out_tile + rbase * C + out_lane;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -462,10 +405,8 @@ __global__ __launch_bounds__(512, 2) void affine_f16x3_kernel(FastArgs a)
                 float v = acc[r] * cscale + addv;
                 if (ACC) v += po[ro];
                 if (a.relu) v = v > 0.f ? v : (v == v ? 0.f : v);
-                if (WC_ABL & 1) asm volatile("" :: "v"(v)); else
                 po[ro] = v;
             }
-            WC_STAMP(2 + 2 * sb);
         };
         // The two waves that share a SIMD (w and w+4) take the staging in opposite halves of the tile: while one is
         // exposed to its vmcnt waits the other is in a pure MFMA stretch, so the matrix pipe keeps running under
@@ -505,19 +446,13 @@ __global__ __launch_bounds__(512, 2) void affine_f16x3_kernel(FastArgs a)
         for (int sb = 0; sb < SUB; ++sb) sub_tile(sb);
         }
         // LDS hand-off only: a raw barrier behind lgkmcnt(0).  __syncthreads() would also drain vmcnt.
-        WC_STAMP(5);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        WC_STAMP(6);
     };
     int t = t_begin;
     for (; t + 2 < t_end; ++t) tile_body(t, T_{}, T_{});
     if (t + 1 < t_end) { tile_body(t, T_{}, F_{}); ++t; }
     tile_body(t, F_{}, F_{});
-    if (WC_STAMPS && a.dbg && lane == 0 && (blockIdx.x == 0 || blockIdx.x == 100)) {
-        unsigned long long* d = a.dbg + ((blockIdx.x ? 1 : 0) * 8 + wave) * 8;
-        for (int i = 0; i < 8; ++i) d[i] = ts[i];
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -542,12 +477,7 @@ __global__ __launch_bounds__(512, 2) void affine_f16x3_kernel(FastArgs a)
 // issued in the first half of tile t-1's loop; younger are the six DMAs of chunks i+1..i+6 (when those exist:
 // t + 3 < n) and the 16 stores at the end of tile t-1: vmcnt(22); fewer DMAs near the end (see WM_).
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef WC_STAGGER
-#define WC_STAGGER 1
-#endif
-#ifndef WC_AHEAD
-#define WC_AHEAD 1      // k-steps between a fragment's ds_read and its MFMAs (2 measured no faster, costs 8 VGPRs)
-#endif
+constexpr int WC_AHEAD = 1;      // k-steps between a fragment's ds_read and its MFMAs (2 measured no faster, costs 8 VGPRs)
 
 // MASK: the epilogue also leaves the ReLU's one-bit gradient mask (a.maskout; relu is then on).  A template parameter, not a
 // branch: as a third epilogue inside one kernel it cost the plain form 7 VGPRs and 32 bytes of scratch.
@@ -563,7 +493,7 @@ __global__ __launch_bounds__(512, 1) void affine_ring_kernel(FastArgs a)
     // (C = 256 on the 16x16x32 shape: 32 bytes -- a row then starts two 16-byte slots further round the banks and the
     // fragment reads of 16 rows x 4 chunks are conflict-free; with 16 bytes every 16-lane group had one 2-way conflict,
     // SQ_LDS_BANK_CONFLICT 40 % of the LDS cycles.  C = 128 has no LDS to spare for the wider pad.)
-    constexpr int PAD = (C == 256 && WC_MFMA16) ? 32 : (C >= 128 ? 16 : 0);
+    constexpr int PAD = C == 256 ? 32 : (C >= 128 ? 16 : 0);
     constexpr int PITCH = C * 2 + PAD;
     constexpr int IMG = TR * PITCH;           // one fp16 image: 16 KiB (+ padding)
     constexpr int FBUF = 2 * IMG;             // hi | lo
@@ -573,8 +503,6 @@ __global__ __launch_bounds__(512, 1) void affine_ring_kernel(FastArgs a)
     char* const ring = smem + 3 * FBUF;
     volatile int* const cnt = reinterpret_cast<volatile int*>(smem + 3 * FBUF + 8 * RAWW);   // [0] converted, [1] read, [2] dirty
 
-    unsigned long long rt_in = 0;
-    if (WC_STAMPS) rt_in = __builtin_amdgcn_s_memrealtime();
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int cg = wave % CG, rg = wave / CG;
@@ -691,16 +619,16 @@ __global__ __launch_bounds__(512, 1) void affine_ring_kernel(FastArgs a)
         }
     };
 
-    // B' fragments.  WC_MFMA16: unit u = 2*s + ch is k-step s (32 deep) of column half ch of this wave's 32 columns; a lane's
+    // B' fragments.  Unit u = 2*s + ch is k-step s (32 deep) of column half ch of this wave's 32 columns; a lane's
     // two output columns are col + 16*ch.  (32x32x16: unit s = k-step s, 16 deep, one column per lane.)
-    constexpr int NCH = WC_MFMA16 ? 2 : 1;
+    constexpr int NCH = 2;
     f16x8 bhi[KS], blo[KS];
     float cscale[NCH], addv[NCH], addv_b[NCH], addv_s[NCH];
 #pragma unroll
     for (int h = 0; h < NCH; ++h) { cscale[h] = 1.f; addv[h] = 0.f; addv_b[h] = 0.f; addv_s[h] = 0.f; }
     int cur_slot = -1;
     const int l15 = lane & 15, lq = lane >> 4;
-    const int col = WC_MFMA16 ? cg * 32 + l15 : cg * 32 + l31;
+    const int col = cg * 32 + l15;
     auto load_b = [&](int slot) {
         const _Float16* ph = a.Bhi + (int64_t)slot * a.slot_stride + ((int64_t)cg * KS * 64 + lane) * 8;
         const _Float16* pl = a.Blo + (int64_t)slot * a.slot_stride + ((int64_t)cg * KS * 64 + lane) * 8;
@@ -758,7 +686,6 @@ __global__ __launch_bounds__(512, 1) void affine_ring_kernel(FastArgs a)
     if (!HAS_SLOT) finish_b();
 
     const int rbase = rg * 32;
-#if WC_MFMA16
     // A fragment of 16 rows x 32 k: lane = row l15 (+ 16 for the second half of the block), 16-byte chunk lq of the k-step
     const int sw = swz(rbase + l15);                    // the same for rows l15 and l15 + 16 (and any 32-row group)
     const int rd_off = (rbase + l15) * PITCH + (PAD ? lq * 16 : 0);
@@ -769,18 +696,8 @@ __global__ __launch_bounds__(512, 1) void affine_ring_kernel(FastArgs a)
     // (l31, l31 + 1) and the ODD lane row +4's columns (l31 - 1, l31): one dword per lane and plane, 64-byte pieces of a row
     const int pl_lane = (rbase + 8 * lh + 4 * (l31 & 1)) * C + cg * 32 + (l31 & ~1);
     const unsigned pl_sel = (l31 & 1) ? 0x03020706u : 0x05040100u;       // v_perm_b32(neighbour, own, sel)
-#else
-    const int sw = swz(rbase + l31);
-    const int rd_off = (rbase + l31) * PITCH;
-    const int out_lane = (rbase + 4 * lh) * C + col;
-#endif
-    unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    bool stamp_on = false;
-    unsigned long long clk0 = 0, rt0 = 0;
-    if (WC_STAMPS) { clk0 = __builtin_amdgcn_s_memtime(); rt0 = __builtin_amdgcn_s_memrealtime(); }
-    if (WC_STAGGER && wave >= 4 && n >= 4) __builtin_amdgcn_s_sleep(24);      // ~half a tile behind waves 0-3
+    if (wave >= 4 && n >= 4) __builtin_amdgcn_s_sleep(24);      // ~half a tile behind waves 0-3
 
-    unsigned long long sum_wait = 0, sum_store = 0;      // WC_STAMPS builds
     int rslot = 4;                     // raw slot of chunk 4(t+1) = chunk 0 of the tile converted during tile t
     int fcur = 0;                      // image buffer of tile t
     using T_ = std::integral_constant<bool, true>;
@@ -792,20 +709,14 @@ __global__ __launch_bounds__(512, 1) void affine_ring_kernel(FastArgs a)
     auto tile_body = [&](int t, auto conv_tag, auto wm_tag) {
         constexpr bool CONV_ = decltype(conv_tag)::value;
         constexpr int WM_ = decltype(wm_tag)::value;
-        stamp_on = WC_STAMPS && (t == 6);
-        WC_STAMP(0);
         const int fnext = fcur == 2 ? 0 : fcur + 1;
         // per-tile opaque copies of the lane constants that feed LDS addresses: without them hipcc hoists every
         // address of every instantiated tile body out of the loop (~60 VGPRs) and spills them
         int sw_t = sw, c4i_t = c4i, lane_t = lane, lh_t = lh, woff_t = woff0, lq_t = lq;
         asm volatile("" : "+v"(sw_t), "+v"(c4i_t), "+v"(lane_t), "+v"(lh_t), "+v"(woff_t), "+v"(lq_t));
         (void)lq_t; (void)lh_t;
-        unsigned long long w0_ = 0;
-        if (WC_STAMPS) w0_ = __builtin_amdgcn_s_memrealtime();
         wait_for(0, 8 * (t + 1));                  // tile t converted by all eight waves (published in mid-loop t-1)
         if (CONV_) wait_for(1, 8 * (t - 1));       // tile t-2 read by all: image buffer (t+1)%3 may be rewritten
-        if (WC_STAMPS) sum_wait += __builtin_amdgcn_s_memrealtime() - w0_;
-        WC_STAMP(1);
         // raw slots of the four chunks converted during this tile
         int rs[4];
 #pragma unroll
@@ -822,7 +733,6 @@ __global__ __launch_bounds__(512, 1) void affine_ring_kernel(FastArgs a)
         };
         const char* hrow = fbuf + fcur * FBUF + rd_off;
         const char* lrow = hrow + IMG;
-#if WC_MFMA16
         // 16x16x32: the wave's 32 x 32 block as 2 x 2 accumulators of 16 x 16; per k-step (32 deep) two A fragments (row
         // halves) x hi/lo = 4 ds_read_b128 (as many as two 16-deep steps took) and 12 MFMAs of 16 cycles in the order
         // lo*Hi, hi*Lo, hi*Hi over the four blocks (a block's accumulator is reused every fourth MFMA).  The shape is
@@ -841,14 +751,13 @@ __global__ __launch_bounds__(512, 1) void affine_ring_kernel(FastArgs a)
 #pragma unroll
         for (int rh = 0; rh < 2; ++rh) { ah[rh] = frag(hrow, rh, 0); al[rh] = frag(lrow, rh, 0); nh[rh] = ah[rh]; nl[rh] = al[rh]; }
         if (CONV_) { chunk_wait(0); craw_read(rs[0], lane_t); }
-        WC_STAMP(2);
         // the conversion of tile t+1 as 20 small steps in the first half of the loop (chunk p: scale+refill, next
         // chunk's read-out, split hi, split lo, write), then its publication
         auto cstep = [&](int j) {
             const int p = j / 5, st = j % 5;
             if (st == 0) {
                 cv_scale();                           // consumes craw: slot rs[p] is free
-                if (p == 0) { if (WC_FENCE_DEP) asm volatile("" :: "v"(cg4[0]) : "memory"); else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }   // chunk 0's ds_read was issued a few instructions ago: it must have RETURNED before the DMA that refills its slot may issue -- with the read only issued, a DMA served from L2 overtook it (one-pass K6, the pair's second workgroup: one corrupted row in ~1e5 tiles)
+                if (p == 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // chunk 0's ds_read was issued a few instructions ago: it must have RETURNED before the DMA that refills its slot may issue -- with the read only issued, a DMA served from L2 overtook it (one-pass K6, the pair's second workgroup: one corrupted row in ~1e5 tiles)
                 const int tl = t + 1 + (p + NSLOT) / 4;
                 if (tl < n) dma_chunk(tl, (p + NSLOT) % 4, rs[p], lane_t);
             } else if (st == 1) {
@@ -865,11 +774,7 @@ __global__ __launch_bounds__(512, 1) void affine_ring_kernel(FastArgs a)
 #pragma unroll
             for (int m = 0; m < 12; ++m) {
                 const int g = 12 * s + m;
-#if WC_M16_ORDER == 1      // row-half major: six MFMAs in a row share the A registers' row half
-                const int rh = m / 6, ch = m & 1, u = 2 * s + ch, pr = (m % 6) >> 1;
-#else                      // product major: a block's accumulator comes round every fourth MFMA
                 const int rh = (m >> 1) & 1, ch = m & 1, u = 2 * s + ch, pr = m >> 2;
-#endif
                 if (pr == 0) acc[rh][ch] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[rh], bhi[u], acc[rh][ch], 0, 0, 0);
                 else if (pr == 1) acc[rh][ch] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rh], blo[u], acc[rh][ch], 0, 0, 0);
                 else acc[rh][ch] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rh], bhi[u], acc[rh][ch], 0, 0, 0);
@@ -892,77 +797,12 @@ __global__ __launch_bounds__(512, 1) void affine_ring_kernel(FastArgs a)
 #pragma unroll
             for (int rh = 0; rh < 2; ++rh) { ah[rh] = nh[rh]; al[rh] = nl[rh]; }
         }
-#else
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        // fragments are fetched TWO k-steps ahead: with eight waves on the LDS a ds_read_b128 takes longer than the
-        // 96 cycles of one k-step's three MFMAs, and an in-order wave that waits for it issues nothing else
-        auto frag = [&](const char* base, int s) {
-            if (PAD) return *reinterpret_cast<const f16x8*>(base + lh_t * 16 + 32 * s);      // lane base + immediate
-            return *reinterpret_cast<const f16x8*>(base + (((2 * s + lh) ^ sw_t) * 16));
-        };
-        constexpr int AHEAD = WC_AHEAD;
-        f16x8 ah = frag(hrow, 0), al = frag(lrow, 0);
-        f16x8 bh_ = ah, bl_ = al;
-        if (KS > 1 && AHEAD == 2) { bh_ = frag(hrow, 1); bl_ = frag(lrow, 1); }
-        if (CONV_) { chunk_wait(0); craw_read(rs[0], lane_t); }
-        WC_STAMP(2);
-        // the conversion of tile t+1 as 20 small steps in the first half of the loop (chunk p: scale+refill, next
-        // chunk's read-out, split hi, split lo, write), then its publication
-        auto cstep = [&](int j) {
-            const int p = j / 5, st = j % 5;
-            if (st == 0) {
-                cv_scale();                           // consumes craw: slot rs[p] is free
-                if (p == 0) { if (WC_FENCE_DEP) asm volatile("" :: "v"(cg4[0]) : "memory"); else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }   // chunk 0's ds_read was issued a few instructions ago: it must have RETURNED before the DMA that refills its slot may issue -- with the read only issued, a DMA served from L2 overtook it (one-pass K6, the pair's second workgroup: one corrupted row in ~1e5 tiles)
-                const int tl = t + 1 + (p + NSLOT) / 4;
-                if (tl < n) dma_chunk(tl, (p + NSLOT) % 4, rs[p], lane_t);
-            } else if (st == 1) {
-                if (p + 1 < 4) { chunk_wait(p + 1); craw_read(rs[p + 1], lane_t); }
-            } else if (st == 2) cv_hi();
-            else if (st == 3) cv_lo();
-            else cv_write(fnext, p, lane_t, c4i_t, woff_t);
-        };
-        constexpr int G = 3 * KS;            // MFMAs = issue gaps per tile
-        constexpr int H = G / 2 > 0 ? G / 2 : 1;
-        // one issue gap = one MFMA plus whatever is listed for it; sched_barrier(0) pins the order gap by gap
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            f16x8 nh = bh_, nl = bl_;
-#pragma unroll
-            for (int m = 0; m < 3; ++m) {
-                const int g = 3 * s + m;
-                if (m == 0) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bhi[s], acc, 0, 0, 0);
-                if (m == 1) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, blo[s], acc, 0, 0, 0);
-                if (m == 2) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bhi[s], acc, 0, 0, 0);
-                if (s + AHEAD < KS) {
-                    if (m == 0) nh = frag(hrow, s + AHEAD);
-                    if (m == 1) nl = frag(lrow, s + AHEAD);
-                }
-                if (CONV_) {
-#pragma unroll
-                    for (int j = 0; j < 21; ++j) {
-                        if ((j * H) / 21 != g) continue;
-                        if (j < 20) cstep(j);
-                        else { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); arrive(0); }
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (AHEAD == 2) { ah = bh_; al = bl_; bh_ = nh; bl_ = nl; }
-            else { ah = nh; al = nl; }
-        }
-#endif
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // my reads of image t are done
         arrive(1);
-        WC_STAMP(3);
         // this wave's 32 x 32 block leaves now: its SIMD partner is half a tile away, in the middle of its MFMAs
         float* po = a.out + (int64_t)tile_of(t) * (TR * C) + out_lane;
         _Float16* pph = nullptr; _Float16* ppl = nullptr;
         if (PL) { pph = a.phi + (int64_t)tile_of(t) * (TR * C) + pl_lane; ppl = a.plo + (int64_t)tile_of(t) * (TR * C) + pl_lane; }
-        unsigned long long s0_ = 0;
-        if (WC_STAMPS) s0_ = __builtin_amdgcn_s_memrealtime();
-#if WC_MFMA16
         // A D register holds 4 rows x 16 columns (64-byte pieces of 4 rows).  v_permlane16_swap of the two column halves'
         // registers gives 2 rows x 32 columns per register again -- 128-byte pieces, the store shape of the 32x32 form.
         // One scalar branch per tile, not one per value (the flag is a kernel argument: tested inside the loop it cut the epilogue
@@ -1002,21 +842,11 @@ __global__ __launch_bounds__(512, 1) void affine_ring_kernel(FastArgs a)
                     const unsigned oh = __builtin_amdgcn_perm(Hn, H, pl_sel), ol = __builtin_amdgcn_perm(Ln, L, pl_sel);
                     unsigned* qh = reinterpret_cast<unsigned*>(pph + (16 * rh + r) * C);
                     unsigned* ql = reinterpret_cast<unsigned*>(ppl + (16 * rh + r) * C);
-#if WC_NT_STORE_PL
-                    __builtin_nontemporal_store(oh, qh);
-                    __builtin_nontemporal_store(ol, ql);
-#else
                     *qh = oh; *ql = ol;
-#endif
                     continue;
                 }
-#if WC_NT_STORE
                 __builtin_nontemporal_store(v0, &po[(16 * rh + r) * C]);
                 __builtin_nontemporal_store(v1, &po[(16 * rh + r + 4) * C]);
-#else
-                po[(16 * rh + r) * C] = v0;          // rows r (lanes 0-31) and 8 + r: columns l31
-                po[(16 * rh + r + 4) * C] = v1;      // rows 4 + r and 12 + r
-#endif
             }
             if (MK) {
                 // lanes l and l + 32 hold the two halves of column l31's 32 row bits (rows +0..7, +16..23 | +8..15, +24..31)
@@ -1033,22 +863,8 @@ __global__ __launch_bounds__(512, 1) void affine_ring_kernel(FastArgs a)
         if (MASK) leave(std::true_type{}, std::true_type{});
         else if (a.relu) leave(std::true_type{}, std::false_type{});
         else leave(std::false_type{}, std::false_type{});
-#else
-        if (a.relu) {       // the ReLU that follows every WC site rides in the epilogue
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float v = acc[r] * cscale[0] + addv[0];
-                po[((r & 3) + 8 * (r >> 2)) * C] = v > 0.f ? v : (v == v ? 0.f : v);
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) po[((r & 3) + 8 * (r >> 2)) * C] = acc[r] * cscale[0] + addv[0];
-        }
-#endif
-        if (WC_STAMPS) sum_store += __builtin_amdgcn_s_memrealtime() - s0_;
         rslot = rs[3] + 1 >= NSLOT ? rs[3] + 1 - NSLOT : rs[3] + 1;
         fcur = fnext;
-        WC_STAMP(4);
     };
     using W0 = std::integral_constant<int, 0>; using W1 = std::integral_constant<int, 1>;
     using W2 = std::integral_constant<int, 2>; using W3 = std::integral_constant<int, 3>;
@@ -1069,28 +885,6 @@ __global__ __launch_bounds__(512, 1) void affine_ring_kernel(FastArgs a)
     pick_table(n - 1);
     tile_body(n - 1, F_{}, W0{});
     const bool overflow = !(gmax <= kF16Guard);
-    if (WC_STAMPS) { ts[6] = __builtin_amdgcn_s_memtime() - clk0; ts[7] = __builtin_amdgcn_s_memrealtime() - rt0; }
-    if (WC_STAMPS && a.dbg && lane == 0 && (blockIdx.x == 0 || blockIdx.x == 100)) {
-        unsigned long long* d = a.dbg + ((blockIdx.x ? 1 : 0) * 8 + wave) * 8;
-        for (int i = 0; i < 8; ++i) d[i] = ts[i];
-    }
-    if (WC_STAMPS && a.dbg && lane == 0 && (wave == 0 || wave == 4))
-        reinterpret_cast<unsigned*>(a.dbg + 384)[blockIdx.x * 2 + (wave >> 2)] = (unsigned)(sum_wait & 0xFFFF) | ((unsigned)(sum_store & 0xFFFF) << 16);
-    if (WC_STAMPS && a.dbg && tid == 0) {      // whole-launch timeline in 10-ns units (s_memrealtime is global)
-        const unsigned long long rt1 = rt0 + ts[7], rt_out = __builtin_amdgcn_s_memrealtime(), big = 1ull << 62;
-        atomicMax(a.dbg + 128, big - rt_in);        // first workgroup start
-        atomicMax(a.dbg + 129, rt_in);              // last workgroup start
-        atomicMax(a.dbg + 130, rt0 - rt_in);        // longest prologue
-        atomicMax(a.dbg + 131, rt_out - rt1);       // longest epilogue
-        atomicMax(a.dbg + 132, big - rt_out);       // first workgroup end
-        atomicMax(a.dbg + 133, rt_out);             // last workgroup end
-        atomicMax(a.dbg + 134, rt1 - rt0);          // longest tile loop
-        atomicMax(a.dbg + 135, big - (rt1 - rt0));  // shortest tile loop
-        // per workgroup: loop time | XCC id << 16 | HW_ID[15:8] (cu, sh, se) << 20
-        const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);
-        const unsigned hwid = __builtin_amdgcn_s_getreg((15 << 11) | (0 << 6) | 4);
-        reinterpret_cast<unsigned*>(a.dbg + 256)[blockIdx.x] = (unsigned)((rt1 - rt0) & 0xFFFF) | (xcc << 16) | (((hwid >> 8) & 0xFF) << 20);
-    }
 
     // Exact redo (rare): of the whole workgroup if anything it staged was outside the fp16 range; and, with slots, of
     // every tile that STRADDLES samples of different slots (HW not a multiple of the tile; the MFMA pass above used the
@@ -1112,11 +906,7 @@ __global__ __launch_bounds__(512, 1) void affine_ring_kernel(FastArgs a)
             const float* xin = a.in + r0 * C;
             float* out_tile = a.out + r0 * C;
             for (int i = 0; i < 16; ++i) {
-#if WC_MFMA16
                 const int row = rbase + 16 * (i >> 3) + 8 * lh + 4 * ((i >> 2) & 1) + (i & 3), ecol = cg * 32 + l31;
-#else
-                const int row = rbase + (i & 3) + 8 * (i >> 2) + 4 * lh, ecol = col;
-#endif
                 int slot = 0;
                 if (HAS_SLOT) slot = a.slot[(r0 + row) / a.HW];
                 const float* Bf = a.Bf + (int64_t)slot * a.bf_stride + ecol;
@@ -1240,11 +1030,10 @@ __global__ __launch_bounds__(512, 1) void onepass_ring_kernel(OnePassArgs a)
         const float* src = (p & 2) ? a.x : a.gy;
         const int64_t row_ = (int64_t)tile_of(tl) * TR + 2 * wave + (p & 1);
         const char* g = reinterpret_cast<const char*>(src + row_ * C) + lane_ * 16;
-        if (XPL && ((p & 2) || (WC_K6_ABL & 512)))      // [hi row | lo row]: 512 bytes of each plane  (ABL 512, timing only: the gradient's chunks too)
+        if (XPL && (p & 2))      // [hi row | lo row]: 512 bytes of each plane  (ABL 512, timing only: the gradient's chunks too)
             g = reinterpret_cast<const char*>(((lane_ >> 5) ? a.xlo : a.xhi) + row_ * C) + (lane_ & 31) * 16;
         const unsigned l = __builtin_amdgcn_readfirstlane(ring_w + slot * 1024);
         unsigned keep;
-        if ((WC_K6_ABL & 256) && (p & 2)) return;   // (development, timing only: no x chunks at all)
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                      : "=&s"(keep) : "v"(g), "s"(l) : "memory");
     };
@@ -1274,7 +1063,7 @@ __global__ __launch_bounds__(512, 1) void onepass_ring_kernel(OnePassArgs a)
     u32x4_ mkw = {0u, 0u, 0u, 0u};          // MK: this lane's four channels' mask words of the tile being converted (read once per tile)
     auto mask_words = [&](int tl) { mkw = *reinterpret_cast<const u32x4_*>(mbuf + (tl % 3) * 1024 + lane * 16); };
     auto cv_scale = [&](int p, int tl) {
-        if (XPL && ((p & 2) || (WC_K6_ABL & 512))) {       // planes: the chunk IS the image's content; held until its write (craw is the next chunk's by then)
+        if (XPL && (p & 2)) {       // planes: the chunk IS the image's content; held until its write (craw is the next chunk's by then)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the read has RETURNED before the slot's refill may issue (no arithmetic here would make hipcc wait)
             cg4 = craw;
             return;
@@ -1297,9 +1086,9 @@ __global__ __launch_bounds__(512, 1) void onepass_ring_kernel(OnePassArgs a)
         gmax = __builtin_fmaxf(__builtin_fmaxf(gmax, fabsf(cg4[0])), fabsf(cg4[1]));
         gmax = __builtin_fmaxf(__builtin_fmaxf(gmax, fabsf(cg4[2])), fabsf(cg4[3]));
     };
-    auto cv_hi = [&](int p) { if (XPL && ((p & 2) || (WC_K6_ABL & 512))) return; chw01 = pk_rne(cg4[0], cg4[1]); chw23 = pk_rne(cg4[2], cg4[3]); };
+    auto cv_hi = [&](int p) { if (XPL && (p & 2)) return; chw01 = pk_rne(cg4[0], cg4[1]); chw23 = pk_rne(cg4[2], cg4[3]); };
     auto cv_lo = [&](int p) {
-        if (XPL && ((p & 2) || (WC_K6_ABL & 512))) return;
+        if (XPL && (p & 2)) return;
         float r0, r1, r2, r3;
         asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(chw01), "v"(cg4[0]));
         asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(chw01), "v"(cg4[1]));
@@ -1312,7 +1101,7 @@ __global__ __launch_bounds__(512, 1) void onepass_ring_kernel(OnePassArgs a)
     const int woff0 = (2 * wave) * PITCH + lane * 8;
     const int xoff0 = (2 * wave) * PITCH + C * 2 + (lane & 31) * 16 + (lane >> 5) * IMG;      // XPL: this lane's 16 bytes of the x half (hi image | lo image)
     auto cv_write = [&](int fb, int p, int woff0_, int xoff0_) {
-        if (XPL && ((p & 2) || (WC_K6_ABL & 512))) {
+        if (XPL && (p & 2)) {
             *reinterpret_cast<f32x4*>(fbuf + fb * FBUF + xoff0_ - ((p & 2) ? 0 : C * 2) + (p & 1) * PITCH) = cg4;
             return;
         }
@@ -1328,7 +1117,6 @@ __global__ __launch_bounds__(512, 1) void onepass_ring_kernel(OnePassArgs a)
         }
     };
     auto wait_for = [&](int which, int target) {
-        if (WC_K6_ABL & 64) return;         // (development: no hand-off waits at all)
         const unsigned addr = cnt_lds + 4u * which;
         for (;;) {
             int v;
@@ -1339,7 +1127,6 @@ __global__ __launch_bounds__(512, 1) void onepass_ring_kernel(OnePassArgs a)
     };
 
     auto wait_both = [&](int target0, int target1) {      // cnt[0] >= target0 and cnt[1] >= target1
-        if (WC_K6_ABL & 64) return;
         for (;;) {
             int2 v;
             asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(cnt_lds) : "memory");
@@ -1404,7 +1191,7 @@ __global__ __launch_bounds__(512, 1) void onepass_ring_kernel(OnePassArgs a)
 
     const int rd_off = l15 * PITCH + lq * 16;
     const int out_lane = (4 * lq) * C + col;          // D register r: row 4 lq + r, column l15 of this wave's 16
-    if (WC_STAGGER && wave >= 4 && n >= 4) __builtin_amdgcn_s_sleep(12);
+    if (wave >= 4 && n >= 4) __builtin_amdgcn_s_sleep(12);
 
     int rslot = 4;
     int fcur = 0;
@@ -1431,7 +1218,6 @@ __global__ __launch_bounds__(512, 1) void onepass_ring_kernel(OnePassArgs a)
 #pragma unroll
         for (int p = 0; p < 4; ++p) { const int v = rslot + p; rs[p] = v >= NSLOT ? v - NSLOT : v; }
         auto chunk_wait = [&](int p) {      // younger vector-memory operations behind chunk p's DMA (header)
-            if (WC_K6_ABL & 32) return;     // (development: what the tile chain costs when no load is ever waited for)
             if (WM_ == 2) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
             else if (WM_ == 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             else if (WM_ == 4 && p == 0) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
@@ -1455,12 +1241,11 @@ __global__ __launch_bounds__(512, 1) void onepass_ring_kernel(OnePassArgs a)
             const int p = j / 5, st = j % 5;
             if (st == 0) {
                 cv_scale(p, t + 1);
-                if (p == 0) { if (WC_FENCE_DEP) asm volatile("" :: "v"(cg4[0]) : "memory"); else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }   // chunk 0's ds_read was issued a few instructions ago: it must have RETURNED before the DMA that refills its slot may issue -- with the read only issued, a DMA served from L2 overtook it (one-pass K6, the pair's second workgroup: one corrupted row in ~1e5 tiles)
+                if (p == 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // chunk 0's ds_read was issued a few instructions ago: it must have RETURNED before the DMA that refills its slot may issue -- with the read only issued, a DMA served from L2 overtook it (one-pass K6, the pair's second workgroup: one corrupted row in ~1e5 tiles)
                 const int tl = t + 1 + (p + NSLOT) / 4;
                 if (tl < n) dma_chunk(tl, (p + NSLOT) % 4, rs[p], lane_t);
             } else if (st == 1) {
                 if (p + 1 < 4) { chunk_wait(p + 1); craw_read(rs[p + 1], lane_t); }
-            } else if (WC_K6_ABL & 8) {
             } else if (st == 2) cv_hi(p);
             else if (st == 3) cv_lo(p);
             else cv_write(fnext, p, woff_t, xoff_t);
@@ -1472,13 +1257,10 @@ __global__ __launch_bounds__(512, 1) void onepass_ring_kernel(OnePassArgs a)
 #pragma unroll
             for (int m = 0; m < 3; ++m) {
                 const int g = 3 * s + m, tb = s >> 3;
-                if (WC_K6_ABL & 2) { asm volatile("" :: "v"(al), "v"(ah), "v"(bhi[s]), "v"(blo[s])); }
-                else {
                 if (m == 0) acc[tb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bhi[s], acc[tb][0], 0, 0, 0);
                 if (m == 1) acc[tb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, blo[s], acc[tb][1], 0, 0, 0);
                 if (m == 2) acc[tb][2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bhi[s], acc[tb][2], 0, 0, 0);
-                }
-                if (s + 1 < KS && !(WC_K6_ABL & 4)) {
+                if (s + 1 < KS) {
                     if (m == 0) nh = frag(hrow, s + 1);
                     if (m == 1) nl = frag(lrow, s + 1);
                 }
@@ -1513,13 +1295,7 @@ __global__ __launch_bounds__(512, 1) void onepass_ring_kernel(OnePassArgs a)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float v0 = (acc[0][0][r] + acc[0][1][r]) + acc[0][2][r], v1 = (acc[1][0][r] + acc[1][1][r]) + acc[1][2][r];
-#if WC_K6_ABL & 1
-            asm volatile("" :: "v"(v0 * cs0v + (v1 * cs1v - subv)), "v"(po));
-#elif WC_NT_STORE_K6
-            __builtin_nontemporal_store(v0 * cs0v + (v1 * cs1v - subv), &po[r * C]);
-#else
             po[r * C] = v0 * cs0v + (v1 * cs1v - subv);
-#endif
         }
         rslot = rs[3] + 1 >= NSLOT ? rs[3] + 1 - NSLOT : rs[3] + 1;
         fcur = fnext;
@@ -1589,7 +1365,7 @@ template <int C>
 hipError_t launch_affine_ring(const FastArgs& a, hipStream_t st)
 {
     constexpr int TR = 8192 / C;
-    constexpr size_t lds = 3 * 2 * (size_t)(TR * (C * 2 + ((C == 256 && WC_MFMA16) ? 32 : (C >= 128 ? 16 : 0)))) + 8 * 7 * 1024 + 64;   // 3 image buffers + 8 x 7 raw chunk slots + counters
+    constexpr size_t lds = 3 * 2 * (size_t)(TR * (C * 2 + (C == 256 ? 32 : (C >= 128 ? 16 : 0)))) + 8 * 7 * 1024 + 64;   // 3 image buffers + 8 x 7 raw chunk slots + counters
     FastArgs b = a;
     b.bias_on = a.bias != nullptr; b.sub_on = a.sub != nullptr;
     if (!b.bias_on) b.bias = a.scale;       // any valid address: loaded and ignored
@@ -1600,21 +1376,16 @@ hipError_t launch_affine_ring(const FastArgs& a, hipStream_t st)
     nwg = (b.ntiles + b.tiles_per_wg - 1) / b.tiles_per_wg;
 #define WC_LAUNCH_RING(SLOT_, MASK_, PL_)                                                                                \
     do {                                                                                                                \
-        static bool attr_set = false;                                                                                   \
-        if (!attr_set) {                                                                                                \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(affine_ring_kernel<C, SLOT_, MASK_, PL_>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                   \
-            if (e != hipSuccess) return e;                                                                              \
-            attr_set = true;                                                                                            \
-        }                                                                                                               \
+        hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(affine_ring_kernel<C, SLOT_, MASK_, PL_>), lds);     \
+        if (e != hipSuccess) return e;                                                                                   \
         hipLaunchKernelGGL((affine_ring_kernel<C, SLOT_, MASK_, PL_>), dim3(nwg), dim3(512), lds, st, b);               \
     } while (0)
-    const bool mask = WC_MFMA16 && b.maskout != nullptr && b.relu;
+    const bool mask = b.maskout != nullptr && b.relu;
     if (b.phi != nullptr) {
         // planes form (C = 128 | 256): the pass itself, then the same kernel behind the gate (leaves at once unless the predicted
         // scale overflowed).  oscale: see wc_launch_out_scale
-        if (!WC_MFMA16 || (C != 128 && C != 256) || nwg > 1024) return hipErrorInvalidValue;
-        if constexpr (WC_MFMA16 && (C == 128 || C == 256)) {
+        if ((C != 128 && C != 256) || nwg > 1024) return hipErrorInvalidValue;
+        if constexpr (C == 128 || C == 256) {
             b.oamax = b.oscale + 2 + kPlaneBounds; b.gate = nullptr; b.ngate = nwg;
             for (int pass = 0; pass < 2; ++pass) {
                 if (b.slot != nullptr) { if (mask) WC_LAUNCH_RING(true, true, true); else WC_LAUNCH_RING(true, false, true); }
@@ -1642,13 +1413,8 @@ hipError_t launch_affine(const FastArgs& a, hipStream_t st)
     nwg = (b.ntiles + b.tiles_per_wg - 1) / b.tiles_per_wg;
 #define WC_LAUNCH_AFFINE(ACC_, SLOT_)                                                                                   \
     do {                                                                                                                \
-        static bool attr_set = false;                                                                                   \
-        if (!attr_set) {                                                                                                \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(affine_f16x3_kernel<C, ACC_, SLOT_>),      \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                   \
-            if (e != hipSuccess) return e;                                                                              \
-            attr_set = true;                                                                                            \
-        }                                                                                                               \
+        hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(affine_f16x3_kernel<C, ACC_, SLOT_>), lds);          \
+        if (e != hipSuccess) return e;                                                                                   \
         hipLaunchKernelGGL((affine_f16x3_kernel<C, ACC_, SLOT_>), dim3(nwg), dim3(512), lds, st, b);                    \
     } while (0)
     const bool has_slot = b.slot != nullptr;
@@ -1667,21 +1433,14 @@ int64_t wc_fast_affine_min_rows()
     return v;
 }
 
-static bool use_ring()
-{
-    static const bool on = getenv("WC_NO_RING") == nullptr;      // development: the register-staged kernel everywhere
-    return on;
-}
-
 bool wc_fast_affine_supported(int64_t N, int64_t HW, int C, bool has_slot)
 {
     if (!(C == 32 || C == 64 || C == 128 || C == 256)) return false;
     const int64_t M = N * HW;
     if (M < wc_fast_affine_min_rows()) return false;
     const int BM = 64 * 256 / C;
-    // slots: the ring kernel (every non-accumulating call) redoes tiles that straddle samples of different slots; the
-    // register-staged kernel cannot, so without the ring a tile must not straddle two samples
-    if (has_slot && !use_ring() && (HW % BM) != 0) return false;
+    // (has_slot adds no condition: the ring kernel, which every non-accumulating call takes, redoes tiles that straddle samples of
+    // different slots)
     if ((M % BM) != 0) return false;                         // whole tiles only (keeps the kernel free of masked accesses)
     return true;
 }
@@ -1689,7 +1448,7 @@ bool wc_fast_affine_supported(int64_t N, int64_t HW, int C, bool has_slot)
 // does wc_launch_fast_affine_planned(relu, relu_mask) write the mask itself?  (the planned ring kernel on the 16x16x32 shape)
 bool wc_fast_affine_writes_mask(int64_t N, int64_t HW, int C)
 {
-    return WC_MFMA16 && use_ring() && wc_fast_affine_supported(N, HW, C, false) && ((N * HW) % (8192 / C)) == 0;
+    return wc_fast_affine_supported(N, HW, C, false) && ((N * HW) % (8192 / C)) == 0;
 }
 
 // ... and can it leave the output as the next convolution's planes (wc_launch_fast_affine_planned(planes, oscale))?
@@ -1759,7 +1518,7 @@ size_t wc_fast_affine_workspace(int C, int Kc)
 {
     // scale[C] | colscale[Kc*C] | hi[Kc*C*C] | lo[Kc*C*C]
     return wc_align_up((size_t)C * 4, 256) + wc_align_up((size_t)Kc * C * 4, 256) +
-           2 * wc_align_up((size_t)Kc * C * C * 2, 256) + 8192;     // + stamp area of WC_STAMPS builds
+           2 * wc_align_up((size_t)Kc * C * C * 2, 256) + 8192;     // (+ 8 KiB: once the stamp area of development builds, kept so that the reported size does not change)
 }
 
 hipError_t wc_launch_channel_scale(const float* in, const float* center, int64_t M, int C, float* scale, hipStream_t st)
@@ -1871,7 +1630,7 @@ hipError_t wc_launch_fast_affine_planned(const float* in, const float* center, c
     // the ring kernel takes any HW: tiles are cut from the M rows, and tiles that straddle samples of different slots
     // are redone with per-row tables at the end of the launch (rare shapes; none of the shipped recipes)
     a.mixed = (a.slot != nullptr && (HW % (8192 / C)) != 0) ? 1 : 0;
-    if (!(accumulate & 1) && use_ring() && ((N * HW) % (8192 / C)) == 0) {
+    if (!(accumulate & 1) && ((N * HW) % (8192 / C)) == 0) {
         switch (C) {
             case 32: return launch_affine_ring<32>(a, st);
             case 64: return launch_affine_ring<64>(a, st);
@@ -1891,8 +1650,7 @@ hipError_t wc_launch_fast_affine_planned(const float* in, const float* center, c
 // K6 in one pass (C = 256, both inputs' scales given, plans of At and of S built): see onepass_ring_kernel
 bool wc_bwd_apply_onepass_supported(int64_t N, int64_t HW, int C)
 {
-    static const bool off = getenv("WC_K6_TWO_PASS") != nullptr;      // development: the two-pass form
-    return !off && WC_MFMA16 && C == 256 && ((N * HW) % 16) == 0 && N * HW >= 4096;
+    return C == 256 && ((N * HW) % 16) == 0 && N * HW >= 4096;
 }
 
 hipError_t wc_launch_bwd_apply_onepass(const float* gy, const float* x, const float* mu, const float* At, int Kc, const float* S,
@@ -1922,13 +1680,8 @@ hipError_t wc_launch_bwd_apply_onepass(const float* gy, const float* x, const fl
     const size_t lds = 3 * 2 * (size_t)(TR * (2 * C * 2 + 32)) + 8 * 7 * 1024 + 64 + (relu_mask ? 3072 : 0);      // + the three shared mask blocks
 #define WC_LAUNCH_ONEPASS(SLOT_, MK_, XPL_)                                                                            \
     do {                                                                                                                \
-        static bool attr_set = false;                                                                                   \
-        if (!attr_set) {                                                                                                \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(onepass_ring_kernel<SLOT_, MK_, XPL_>),    \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                   \
-            if (e != hipSuccess) return e;                                                                              \
-            attr_set = true;                                                                                            \
-        }                                                                                                               \
+        hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(onepass_ring_kernel<SLOT_, MK_, XPL_>), lds);        \
+        if (e != hipSuccess) return e;                                                                                   \
         hipLaunchKernelGGL((onepass_ring_kernel<SLOT_, MK_, XPL_>), dim3(groups16 * 16), dim3(512), lds, st, a);        \
     } while (0)
     if (xs) {

@@ -32,37 +32,12 @@ __device__ __forceinline__ unsigned pk_rne(float a, float b)
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));
 }
 constexpr float kGuard = 60000.0f;
-#ifndef XTY_ROLE31
-#define XTY_ROLE31 1    // K4 on planes, quadrant form: the waves that stage X (one v_perm per image word) own three blocks of their block row, the waves that
-#endif                  // stage and convert gy one -- see the stage loop.  0: two blocks each (rounds 4-5), for A/B
-#ifndef XTY_STAMPS
-#define XTY_STAMPS 0      // development: s_memtime stamps of wave 0 / workgroup 0 behind the partials (the caller adds 2 KiB to the workspace)
-#endif
 constexpr int BW_PLAIN = 3;                // 32x32 blocks per wave
-#ifndef XTY_BAL
-#define XTY_BAL 1
-#endif
-#ifndef XTY_ALLLIVE
-#define XTY_ALLLIVE 1
-#endif
-#ifndef XTY_ALT
-#define XTY_ALT 0       // 1: covariance (K1): every other MFMA chain runs on the NEGATED A fragments and is subtracted at the float64 flush (see the stage loop)
-#endif
-#ifndef XTY_FLUSH_STAGES
-#define XTY_FLUSH_STAGES 1     // covariance (K1): stages per fp32 MFMA chain before the float64 flush.  Development knob, measured in round 3
-                               // (tools/seed_sweep.py, worst dx over three seeds at 128x32x32x256, cond 1e6): 1 stage = 12 MFMA accumulations
-                               // 1.39e-4; 2 stages 1.72e-4; 4 stages 2.19e-4; 16 stages 1.03e-3 -- and SHORTER chains (a flush every 2 k-steps /
-                               // every k-step, built and dropped) 1.92e-4 / 3.23e-4: one stage per chain is the optimum of this scheme
-#endif
-#ifndef XTY_YPL_ABL
-#define XTY_YPL_ABL 0   // development, TIMING ONLY (wrong results): K4 on planes stages the gradient operand from planes as well (it reads x's planes again) --
-#endif                  // what K4 would cost if the gradient arrived pre-masked and pre-split (ranked first for round 6)
-#ifndef XTY_LOLO
-#define XTY_LOLO 0      // 1: covariance (K1): the fourth product lo*lo on every block (round 5, VERDICT r4 item 7: the lever named for the non-gaussian families)
-#endif
-#ifndef XTY_SUBFLUSH
-#define XTY_SUBFLUSH 1  // covariance (K1): float64 flushes per stage -- 2 = a flush every KS/2 k-steps (chains of 6 accumulations instead of 12)
-#endif
+// K4 on planes, quadrant form: the waves that stage X (one v_perm per image word) own three blocks of their block row, the waves that
+// stage and convert gy one -- see the stage loop.  (Two blocks each in rounds 4-5.)
+// Covariance (K1): one stage per fp32 MFMA chain before the float64 flush (12 accumulations).  Measured in round 3 (tools/seed_sweep.py,
+// worst dx over three seeds at 128x32x32x256, cond 1e6): 1 stage 1.39e-4; 2 stages 1.72e-4; 4 stages 2.19e-4; 16 stages 1.03e-3 -- and
+// SHORTER chains (a flush every 2 k-steps / every k-step, built and dropped) 1.92e-4 / 3.23e-4: one stage per chain is the optimum.
 template <int C, bool TWO> constexpr bool xty_quad() { return TWO && C == 256; }
 
 // The off-diagonal sums of the covariance kernel come out of the matrix pipe LOW by a nearly constant 8-10 e-10 of sqrt(S_ii S_jj)
@@ -75,7 +50,7 @@ template <int C, bool TWO> constexpr bool xty_quad() { return TWO && C == 256; }
 //   uniform(-1, 1) -5.9e-10, C = 64 gaussian -5.8e-10
 // The compensation adds kappa sqrt(S_ii S_jj) back to every off-diagonal sum (stats_xtx_kernel): with kappa in the middle of that
 // range the residual bias is <= 1/3 of the uncompensated one for every input above.  It belongs to THIS kernel's accumulation
-// scheme (three products into one fp32 accumulator, 12 accumulations per chain, XTY_FLUSH_STAGES 1): re-measure when that changes.
+// scheme (three products into one fp32 accumulator, 12 accumulations per chain): re-measure when that changes.
 constexpr double kXtyOffdiagBias = 8.5e-10;
 
 
@@ -120,8 +95,8 @@ __global__ __launch_bounds__(512, 1) void xty_f16x3_kernel(FastXtyArgs a)
     // the plain scheme convert all of it three times), its images hold twice the rows (64 per stage: half the barriers)
     // and a wave owns 2 blocks instead of 3 (no idle block slots: 64 = 4 x 8 x 2).
     constexpr bool QUAD = xty_quad<C, TWO>();
-    constexpr bool BAL = XTY_BAL && !TWO && C == 256;     // (two workgroup types, 36 blocks)
-    constexpr bool BAL2 = XTY_BAL && TWO && C == 128;
+    constexpr bool BAL = !TWO && C == 256;     // (two workgroup types, 36 blocks)
+    constexpr bool BAL2 = TWO && C == 128;
     constexpr int BW = QUAD ? 2 : BW_PLAIN;           // 32x32 blocks per wave
     constexpr int CS = QUAD ? C / 2 : C;              // channels of an operand that this workgroup stages
     constexpr int C4 = CS / 4;
@@ -194,7 +169,7 @@ __global__ __launch_bounds__(512, 1) void xty_f16x3_kernel(FastXtyArgs a)
     bool all_ = true, any_ = false;
 #pragma unroll
     for (int b = 0; b < BW; ++b) { all_ = all_ && live[b]; any_ = any_ || live[b]; }
-    const bool all_live = XTY_ALLLIVE && (QUAD || __builtin_amdgcn_readfirstlane(all_ ? 1 : 0) != 0);
+    const bool all_live = QUAD || __builtin_amdgcn_readfirstlane(all_ ? 1 : 0) != 0;
     const bool two_live = (BAL || BAL2) && __builtin_amdgcn_readfirstlane((live[0] && live[1] && !live[BW - 1]) ? 1 : 0) != 0;   // blocks 0, 1 only      // wave-uniform by construction (wave index, type)
     const bool any_live = QUAD || __builtin_amdgcn_readfirstlane(any_ ? 1 : 0) != 0;
 
@@ -236,7 +211,7 @@ __global__ __launch_bounds__(512, 1) void xty_f16x3_kernel(FastXtyArgs a)
     f32x4 yr[RELU == 1 ? 8 : 1];
     uint4 ym0 = {0u, 0u, 0u, 0u};
     const bool y_wave = RELU && __builtin_amdgcn_readfirstlane(op) != 0;       // waves 4-7 stage Y (wave-uniform: a scalar branch)
-    const bool x_wave = XPL && (XTY_YPL_ABL || __builtin_amdgcn_readfirstlane(op) == 0);        // waves 0-3 stage X (wave-uniform: a scalar branch)
+    const bool x_wave = XPL && __builtin_amdgcn_readfirstlane(op) == 0;        // waves 0-3 stage X (wave-uniform: a scalar branch)
     // (RL: 0 = the wave's role is a run-time value, as in every form but ROLE31; 1 = an X wave, 2 = a Y wave at compile time -- each role's loop
     //  then holds only its own staging code and registers)
     auto stage_load = [&](int st, auto RL_, f32x4 (&xr)[8], uint4& ym) __attribute__((always_inline)) {
@@ -384,7 +359,7 @@ __global__ __launch_bounds__(512, 1) void xty_f16x3_kernel(FastXtyArgs a)
     }
 
     using RL0 = std::integral_constant<int, 0>;
-    constexpr bool ROLE31 = XTY_ROLE31 && QUAD && (XPL || RELU == 2) && !XTY_YPL_ABL && !XTY_STAMPS;      // (tried on the C = 128 planes form -- one 4 x 4 block grid, a quadrant's geometry: 47.1 -> 48.8 / 66.2 -> 68.7 us per stage, not taken)      // (fp32 x with the bit mask: both roles convert -- two blocks
+    constexpr bool ROLE31 = QUAD && (XPL || RELU == 2);      // (tried on the C = 128 planes form -- one 4 x 4 block grid, a quadrant's geometry: 47.1 -> 48.8 / 66.2 -> 68.7 us per stage, not taken)      // (fp32 x with the bit mask: both roles convert -- two blocks
                                                                                                            //  and two sets each: 103 -> 98 us; without a mask the old loop is as fast: 81 against 83)
     if (!ROLE31 && nst > 0) {
         stage_load(0, RL0{}, xr0, ym0);
@@ -392,11 +367,6 @@ __global__ __launch_bounds__(512, 1) void xty_f16x3_kernel(FastXtyArgs a)
         if (nst > 1) stage_load(1, RL0{}, xr0, ym0);
     }
     if (!ROLE31) __syncthreads();
-    const bool stamp_ok = XTY_STAMPS && tid == 0 && blockIdx.x == 0;
-    unsigned long long* stamps = reinterpret_cast<unsigned long long*>(a.P + (int64_t)a.nslab * C * C);     // just past P: stamp builds get a larger workspace
-    int nstamp = 0;
-    (void)stamps; (void)nstamp; (void)stamp_ok;
-#define XS() do { if (XTY_STAMPS && stamp_ok && nstamp < 250) stamps[nstamp++] = __builtin_amdgcn_s_memtime(); } while (0)
     // (Tried and dropped, measured: the stage as two half-steps in which waves 0-3 convert while their SIMD partners 4-7 run the
     // MFMAs and vice versa -- both halves slowed down by more than 2x, K1 89 -> 127 us: the ds_write_b128 bursts of the
     // converting waves and the fragment reads of the MFMA waves fight over the LDS.  An L2 prefetch of the stage three steps
@@ -405,20 +375,14 @@ __global__ __launch_bounds__(512, 1) void xty_f16x3_kernel(FastXtyArgs a)
     f32x16 acc[BW];
     for (int st = 0; !ROLE31 && st < nst; ++st) {
         const int cur = st & 1;
-        XS();
         if (st + 1 < nst) stage_write(cur ^ 1, st + 1, RL0{}, xr0, ym0);
-        XS();
         if (st + 2 < nst) stage_load(st + 2, RL0{}, xr0, ym0);
-        XS();
         // the fp32 accumulators live for one stage only (their first MFMA takes a zero operand: no zeroing pass, and the 16 BW
         // registers are free while the next stage is converted)
-        constexpr int FS = TWO ? 1 : XTY_FLUSH_STAGES;
-        if (FS == 1 || st % FS == 0) {
 #pragma unroll
-            for (int b = 0; b < BW; ++b)
+        for (int b = 0; b < BW; ++b)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-        }
+            for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
         const int kbuf = cur << 16;
         auto frag = [&](int base, int ks, int lo) __attribute__((always_inline)) {
             return *reinterpret_cast<const f16x8*>(smem + (base ^ ((ks << 5) | kbuf)) + lo * IMG);
@@ -426,30 +390,16 @@ __global__ __launch_bounds__(512, 1) void xty_f16x3_kernel(FastXtyArgs a)
         // ALL: every block of this wave is live (a scalar, per wave) -- the loop is then ONE basic block; with a `live` test per
         // block and k-step (a per-lane value as far as hipcc can tell: exec-mask branches) every three MFMAs sat in a block of
         // their own (K1 kernel 60 -> 56 us)
-        // XTY_ALT (round 4): v_mfma_f32_32x32x16_f16's accumulation is biased -- every chain comes out low by ~1e-9 of sqrt(S_ii S_jj)
-        // whatever the sign of its sum (rounds 3-4 added a fitted constant back) -- so every ODD stage runs on the
-        // negated A fragments and its chain is SUBTRACTED at the flush: the sums add up as before, the biases of consecutive chains
-        // cancel (measured: mean off-diagonal error -9.7e-10 -> +5e-12 of sqrt(S_ii S_jj), the same on uniform / post-ReLU / Laplace
-        // inputs).  The f16 MFMAs have no neg modifier: one v_xor per fragment register with a wave-uniform mask (0 in even stages).
-        const unsigned sgn = (XTY_ALT && !TWO && FS == 1 && (st & 1)) ? 0x80008000u : 0u;
-        constexpr int NSUB = (!TWO && XTY_SUBFLUSH > 1 && KS % XTY_SUBFLUSH == 0) ? XTY_SUBFLUSH : 1;
-        int ks_lo = 0, ks_hi = KS;
         auto products = [&](auto ALL_, auto NL_) __attribute__((always_inline)) {
             constexpr bool ALL = decltype(ALL_)::value;
             constexpr int NL = decltype(NL_)::value;          // blocks 0 .. NL-1 (all live when ALL)
 #pragma unroll 4
-            for (int ks = ks_lo; ks < ks_hi; ++ks) {
+            for (int ks = 0; ks < KS; ++ks) {
 #pragma unroll
                 for (int b = 0; b < NL; ++b) {
                     if (!ALL && !live[b]) continue;
                     f16x8 ah = frag(a_base[b], ks, 0), al = frag(a_base[b], ks, 1);
-                    if (XTY_ALT && !TWO && FS == 1 && sgn) {       // (a scalar branch: even stages skip the eight v_xor)
-                        typedef unsigned u32x4v_ __attribute__((ext_vector_type(4)));
-                        ah = __builtin_bit_cast(f16x8, __builtin_bit_cast(u32x4v_, ah) ^ sgn);
-                        al = __builtin_bit_cast(f16x8, __builtin_bit_cast(u32x4v_, al) ^ sgn);
-                    }
                     const f16x8 bh = frag(b_base[b], ks, 0), bl = frag(b_base[b], ks, 1);
-                    if (XTY_LOLO && !TWO) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bl, acc[b], 0, 0, 0);
                     acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[b], 0, 0, 0);
                     acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[b], 0, 0, 0);
                     acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[b], 0, 0, 0);
@@ -473,43 +423,25 @@ __global__ __launch_bounds__(512, 1) void xty_f16x3_kernel(FastXtyArgs a)
                 }
             }
         };
-        const double fsg = sgn ? -1.0 : 1.0;             // (wave-uniform: the chain's sign)
-#pragma unroll
-        for (int sub = 0; sub < NSUB; ++sub) {
-        if (NSUB > 1) {
-            ks_lo = sub * (KS / NSUB); ks_hi = ks_lo + KS / NSUB;
-            if (sub > 0) {
-#pragma unroll
-                for (int b = 0; b < BW; ++b)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-            }
-        }
         if (QUAD) products_quad();
         else if (all_live) products(std::true_type{}, std::integral_constant<int, BW>{});
         else if (two_live) products(std::true_type{}, std::integral_constant<int, 2>{});
         else if (any_live) products(std::false_type{}, std::integral_constant<int, BW>{});
-        XS();
         // float64 flush: the fp32 rounding chain never exceeds one stage (3*KS MFMA accumulations)
-        if (FS > 1 && st % FS != FS - 1 && st + 1 < nst) {}
-        else if (two_live) {
+        if (two_live) {
 #pragma unroll
             for (int b = 0; b < 2; ++b)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc64[b][r] = __builtin_fma((double)acc[b][r], fsg, acc64[b][r]);
+                for (int r = 0; r < 16; ++r) acc64[b][r] = __builtin_fma((double)acc[b][r], 1.0, acc64[b][r]);
         } else if (any_live) {
 #pragma unroll
             for (int b = 0; b < BW; ++b)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc64[b][r] = __builtin_fma((double)acc[b][r], fsg, acc64[b][r]);
+                for (int r = 0; r < 16; ++r) acc64[b][r] = __builtin_fma((double)acc[b][r], 1.0, acc64[b][r]);
         }
-        }
-        XS();
         // LDS hand-off only (__syncthreads() would also drain vmcnt, i.e. wait for the loads of stage st+2 issued a moment ago)
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
-    if (XTY_STAMPS && stamp_ok) { stamps[nstamp++] = __builtin_amdgcn_s_memtime(); stamps[255] = nstamp; }
-#undef XS
 
     // partial blocks out, scales undone exactly (powers of two)
     double* P = a.P + z * (int64_t)C * C;
@@ -584,7 +516,7 @@ __global__ __launch_bounds__(512, 1) void xty_f16x3_kernel(FastXtyArgs a)
                 asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             };
             // (the X role with three blocks has no room for a second set: its plane rows keep one stage in flight, the Y role's fp32 rows two)
-            constexpr bool TWOSETS = XTY_ROLE31 == 2 || RLt::value == 2 || !XPL;
+            constexpr bool TWOSETS = RLt::value == 2 || !XPL;
             if constexpr (TWOSETS) {
                 if (nst > 0) {
                     stage_load(0, RLt{}, xr0, ym0);
@@ -628,7 +560,7 @@ __global__ __launch_bounds__(512, 1) void xty_f16x3_kernel(FastXtyArgs a)
                 }
             }
         };
-        constexpr int NBX = (XPL && XTY_ROLE31 == 3) ? 4 : (XPL && XTY_ROLE31 != 2) ? 3 : 2;          // (XTY_ROLE31 == 2 / 3, development: two / four blocks per X wave on planes)
+        constexpr int NBX = XPL ? 3 : 2;          // blocks per X wave
         if (__builtin_amdgcn_readfirstlane(op) == 0) role(std::integral_constant<int, NBX>{}, std::integral_constant<int, 1>{});
         else role(std::integral_constant<int, 4 - NBX>{}, std::integral_constant<int, 2>{});
     }
@@ -685,13 +617,8 @@ hipError_t launch_xty_fast(const FastXtyArgs& a, hipStream_t st)
 {
     constexpr int R = stage_rows<C, TWO>();
     constexpr size_t lds = (size_t)2 * (TWO ? 2 : 1) * 2 * (xty_quad<C, TWO>() ? C / 2 : C) * R * 2;       // 128 KiB
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(xty_f16x3_kernel<C, TWO, RELU, XPL>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(xty_f16x3_kernel<C, TWO, RELU, XPL>), lds);
+    if (e != hipSuccess) return e;
     const int slab_groups = (a.nslab + 7) / 8;
     const int grid = slab_groups * a.ntypes * 8;
     hipLaunchKernelGGL((xty_f16x3_kernel<C, TWO, RELU, XPL>), dim3(grid), dim3(512), lds, st, a);
@@ -776,6 +703,5 @@ hipError_t wc_launch_fast_xty(const float* X, const float* Y, const float* cx, c
 
 double wc_fast_xty_offdiag_bias(void)
 {
-    static const char* off = getenv("WC_K1_NO_BIAS_COMP");       // development: the uncompensated sums (tools/k1_bias_survey.py)
-    return off ? 0.0 : kXtyOffdiagBias;
+    return kXtyOffdiagBias;
 }

@@ -46,14 +46,11 @@ constexpr float kResGuard = 60000.0f;
 
 // The tensors these kernels write (planes, the fp32 sum) are streams far larger than the L2s that nobody reads before the launch ends: they leave
 // as NON-TEMPORAL stores (round 6: the fused producer 86.5 -> 75.9 us per call at 128 x 32 x 32 x 256 -- a wave's loads and stores retire on one
-// in-order counter, so a store that is acknowledged sooner also releases the rows requested behind it).  WC_RX_NT=0: plain stores, for A/B.
-#ifndef WC_RX_NT
-#define WC_RX_NT 1
-#endif
+// in-order counter, so a store that is acknowledged sooner also releases the rows requested behind it).
 template <typename V>
 __device__ __forceinline__ void st_stream(V* p, V v)
 {
-    if (WC_RX_NT) __builtin_nontemporal_store(v, p); else *p = v;
+    __builtin_nontemporal_store(v, p);
 }
 typedef unsigned u32x2r __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4r __attribute__((ext_vector_type(4)));
@@ -278,12 +275,6 @@ __global__ __launch_bounds__(256) void resadd_kernel(ResAddArgs a)
 // The partials P / colsum / dfix go where wc_whiten_split_f16x2's tail expects them (wc_whiten_presummed_f16x2 runs that tail), so the
 // site's K1 launch does not exist.  Saturation: as resadd_kernel -- the channel's true maximum is recorded, the gated second launch
 // redoes planes AND partials with the lowered scales.
-#ifndef WC_RX_STAGGER
-#define WC_RX_STAGGER 1      // 0: every wave converts first (round 5)
-#endif
-#ifndef WC_RX_ABL
-#define WC_RX_ABL 0      // development ablation bits (wrong results, times only): 1 no plane stores, 2 no shortcut rows, 4 no MFMAs, 8 no float64 flush, 16 the planes as 16-byte stores (misplaced)
-#endif
 
 struct ResXtxArgs {
     ResAddArgs r;                          // h, s, geometry, centre / scale / flag area, planes, x32
@@ -292,7 +283,6 @@ struct ResXtxArgs {
     int64_t rows_per_slab;
     int nslab, ntypes;
     double* P; float* colsum; double* dfix;
-    int sample_inside;                     // 1: every workgroup takes centre / scales from the <= 256 sampled rows itself (no resadd_sample_kernel launch)
     int* wgflag; float* wgmax;             // [grid], [grid][C]: per-workgroup "an element did not fit" and that workgroup's per-channel maxima (pass 1 -> gate)
 };
 
@@ -465,32 +455,30 @@ __global__ __launch_bounds__(512, 1) void resadd_xtx_kernel(ResXtxArgs a)
     const int c4 = tid % C4, rgrp = tid / C4;
     if (tid < C) ov_sh[tid] = 0u;
     if (tid == 0) ov_sh[C] = 0u;
-    if (!REDO && a.sample_inside) {
+    if (!REDO) {        // every workgroup takes centre / scales from the <= 256 sampled rows itself (no resadd_sample_kernel launch)
         rx_sample<C>(a.r, smem, sc_sh, nc_sh, tid, z == 0 && type == 0);
         cs_acc[tid] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < 4; ++j) sq_acc[tid * 4 + j] = 0.0;
-    } else {
-        f32x4 scl = *reinterpret_cast<const f32x4*>((REDO ? a.r.scale0 : a.r.scale) + 4 * c4);
-        if (REDO) {         // the scales the true maxima ask for (resadd_kernel's rule); the first slab's type-0 workgroup stores them
-            f32x4 gm4 = {0.f, 0.f, 0.f, 0.f};       // the channel's maximum over the workgroups that reported one (rare path: a plain loop)
-            for (int i = 0; i < (int)gridDim.x; ++i)
-                if (a.wgflag[i]) {
-                    const f32x4 w = *reinterpret_cast<const f32x4*>(a.wgmax + (int64_t)i * C + 4 * c4);
+    } else {        // REDO: the scales the true maxima ask for (resadd_kernel's rule); the first slab's type-0 workgroup stores them
+        f32x4 scl = *reinterpret_cast<const f32x4*>(a.r.scale0 + 4 * c4);
+        f32x4 gm4 = {0.f, 0.f, 0.f, 0.f};       // the channel's maximum over the workgroups that reported one (rare path: a plain loop)
+        for (int i = 0; i < (int)gridDim.x; ++i)
+            if (a.wgflag[i]) {
+                const f32x4 w = *reinterpret_cast<const f32x4*>(a.wgmax + (int64_t)i * C + 4 * c4);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) gm4[j] = fmaxf(gm4[j], w[j]);
-                }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float gm = gm4[j];
-                if (gm > 0.f && gm < 3.0e38f) {
-                    int e;
-                    frexpf(gm, &e);
-                    scl[j] *= ldexpf(1.0f, 15 - e);
-                }
+                for (int j = 0; j < 4; ++j) gm4[j] = fmaxf(gm4[j], w[j]);
             }
-            if (z == 0 && type == 0 && rgrp == 0) *reinterpret_cast<f32x4*>(a.r.scale + 4 * c4) = scl;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float gm = gm4[j];
+            if (gm > 0.f && gm < 3.0e38f) {
+                int e;
+                frexpf(gm, &e);
+                scl[j] *= ldexpf(1.0f, 15 - e);
+            }
         }
+        if (z == 0 && type == 0 && rgrp == 0) *reinterpret_cast<f32x4*>(a.r.scale + 4 * c4) = scl;
         if (rgrp == 0) {
             *reinterpret_cast<f32x4*>(sc_sh + 4 * c4) = scl;
             *reinterpret_cast<f32x4*>(nc_sh + 4 * c4) = -(*reinterpret_cast<const f32x4*>(a.r.center + 4 * c4)) * scl;
@@ -534,7 +522,7 @@ __global__ __launch_bounds__(512, 1) void resadd_xtx_kernel(ResXtxArgs a)
         const float* base = g_h + row0 * C + 4 * c4;
 #pragma unroll
         for (int p = 0; p < 8; ++p) xr[p] = *reinterpret_cast<const f32x4*>(base + p * C);
-        if (has_s && !(WC_RX_ABL & 2)) {
+        if (has_s) {
             const float* sb = g_s + src_row_l((unsigned)row0) * C + 4 * c4;
 #pragma unroll
             for (int p = 0; p < 4; ++p) sr[p] = *reinterpret_cast<const f32x4*>(sb + p * C);
@@ -552,7 +540,7 @@ __global__ __launch_bounds__(512, 1) void resadd_xtx_kernel(ResXtxArgs a)
 #pragma unroll
         for (int p = 0; p < 8; ++p) {
             f32x4 v = xr[p];
-            if (has_s && !(WC_RX_ABL & 2)) v += sr[p >> 1];
+            if (has_s) v += sr[p >> 1];
             if (F32 && st_hi) st_stream(reinterpret_cast<f32x4*>(g_x32 + (row0 + p) * C + 4 * c4), v);
             g[p] = v * scl + ncs;
         }
@@ -603,24 +591,13 @@ __global__ __launch_bounds__(512, 1) void resadd_xtx_kernel(ResXtxArgs a)
                 asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(q1) : "v"(H[p][w]), "v"(v1));
                 Lw[p][w] = pk_rne2r(q0, q1);
             }
-        if (WC_RX_ABL & 16) {        // timing only: the same bytes as four 16-byte stores per plane (rows p, p + 1 are 1 KiB contiguous; data misplaced)
-            if (st_hi) {
+        if (st_hi) {
 #pragma unroll
-                for (int p = 0; p < 8; p += 2) *reinterpret_cast<uint4*>(g_hi + (row0 + p) * C + 8 * c4) = make_uint4(H[p][0], H[p][1], H[p + 1][0], H[p + 1][1]);
-            }
-            if (st_lo) {
+            for (int p = 0; p < 8; ++p) st_stream(reinterpret_cast<u32x2r*>(g_hi + (row0 + p) * C + 4 * c4), u32x2r{H[p][0], H[p][1]});
+        }
+        if (st_lo) {
 #pragma unroll
-                for (int p = 0; p < 8; p += 2) *reinterpret_cast<uint4*>(g_lo + (row0 + p) * C + 8 * c4) = make_uint4(Lw[p][0], Lw[p][1], Lw[p + 1][0], Lw[p + 1][1]);
-            }
-        } else if (!(WC_RX_ABL & 1)) {
-            if (st_hi) {
-#pragma unroll
-                for (int p = 0; p < 8; ++p) st_stream(reinterpret_cast<u32x2r*>(g_hi + (row0 + p) * C + 4 * c4), u32x2r{H[p][0], H[p][1]});
-            }
-            if (st_lo) {
-#pragma unroll
-                for (int p = 0; p < 8; ++p) st_stream(reinterpret_cast<u32x2r*>(g_lo + (row0 + p) * C + 4 * c4), u32x2r{Lw[p][0], Lw[p][1]});
-            }
+            for (int p = 0; p < 8; ++p) st_stream(reinterpret_cast<u32x2r*>(g_lo + (row0 + p) * C + 4 * c4), u32x2r{Lw[p][0], Lw[p][1]});
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -698,12 +675,10 @@ __global__ __launch_bounds__(512, 1) void resadd_xtx_kernel(ResXtxArgs a)
                     }
                 };
                 const bool all_here = NBK == BW ? all_live : two_live;          // every slot of this copy live (a scalar per wave)
-                if (WC_RX_ABL & 4) {}
-                else if (all_here) products(std::true_type{}, std::integral_constant<int, NBK>{});
+                if (all_here) products(std::true_type{}, std::integral_constant<int, NBK>{});
                 else if (NBK == BW && two_live) products(std::true_type{}, std::integral_constant<int, NBK < 2 ? NBK : 2>{});
                 else if (any_live) products(std::false_type{}, std::integral_constant<int, NBK>{});
-                if (WC_RX_ABL & 8) {}
-                else if (NBK == BW && two_live) {
+                if (NBK == BW && two_live) {
 #pragma unroll
                     for (int b = 0; b < (NBK < 2 ? NBK : 2); ++b)
 #pragma unroll
@@ -735,7 +710,7 @@ __global__ __launch_bounds__(512, 1) void resadd_xtx_kernel(ResXtxArgs a)
     };
     constexpr int NBK_B = BAL ? 2 : 0;            // waves 4-7: two blocks each (C = 256, balanced) | none ((type * 8 + wave) * 3 >= 10 at C = 128)
     static_assert(BAL || (4 * BW >= NBLK), "C = 128: waves 4-7 own no block");
-    if (WC_RX_STAGGER && wave >= 4) run(std::true_type{}, std::integral_constant<int, NBK_B>{});
+    if (wave >= 4) run(std::true_type{}, std::integral_constant<int, NBK_B>{});
     else run(std::false_type{}, std::integral_constant<int, BW>{});
     // column sums / the diagonal: the row groups' per-thread sums are already in LDS, thread (rgrp, c4) at slot tid = rgrp * C4 + c4
     __syncthreads();
@@ -891,21 +866,12 @@ hipError_t wc_launch_resadd_xtx(const float* h, const float* s, int64_t N, int64
     a.N = groups; a.HW = r.M / groups; a.per_sample = groups > 1; a.nsplit = nsplit; a.rows_per_slab = rows_per_slab;
     a.nslab = nslab; a.ntypes = ntypes; a.P = P; a.colsum = colsum; a.dfix = dfix;
     a.wgflag = wgflag; a.wgmax = wgmax;
-    // WC_RX_SAMPLE_KERNEL=1 (development, A/B): centre / scales from a launch of resadd_sample_kernel in front, as wc_resadd_split_f32 has it
-    static const bool sample_launch = getenv("WC_RX_SAMPLE_KERNEL") && atoi(getenv("WC_RX_SAMPLE_KERNEL")) != 0;
-    a.sample_inside = sample_launch ? 0 : 1;
-    if (sample_launch) hipLaunchKernelGGL(resadd_sample_kernel, dim3((C + kSampCh - 1) / kSampCh), dim3(256), 0, st, r);
     const size_t lds = 131072 + 512 * 48 + 2 * (size_t)C * 4 + ((size_t)C + 4) * 4;
     const int grid = wc_resadd_xtx_grid(nslab, ntypes);
 #define WC_LAUNCH_RX(C_, F_, R_)                                                                                                   \
     do {                                                                                                                           \
-        static bool attr_set = false;                                                                                              \
-        if (!attr_set) {                                                                                                           \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(resadd_xtx_kernel<C_, F_, R_>),                       \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                              \
-            if (e != hipSuccess) return e;                                                                                         \
-            attr_set = true;                                                                                                       \
-        }                                                                                                                          \
+        hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(resadd_xtx_kernel<C_, F_, R_>), lds);                         \
+        if (e != hipSuccess) return e;                                                                                             \
         hipLaunchKernelGGL((resadd_xtx_kernel<C_, F_, R_>), dim3(grid), dim3(512), lds, st, a);                                    \
     } while (0)
     if (C == 256) {

@@ -609,15 +609,8 @@ __global__ __launch_bounds__(256) void mask_from_y_kernel(const float* __restric
 __global__ __launch_bounds__(256) void stream_copy_kernel(const f32x4* __restrict__ src, f32x4* __restrict__ dst, int64_t n4)
 {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-#ifndef WC_NT_COPY
-#define WC_NT_COPY 1      // the stream-copy yardstick gets the same nontemporal stores as K3's epilogue (40.8 -> 40.5 us)
-#endif
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-#if WC_NT_COPY
         __builtin_nontemporal_store(src[i], &dst[i]);
-#else
-        dst[i] = src[i];
-#endif
     }
 }
 
@@ -671,13 +664,8 @@ hipError_t wc_launch_xty(const WcXtyArgs& a, int nslab, hipStream_t st)
         const int nb = (a.C + XT - 1) / XT;
         const int ntiles = a.sym ? nb * (nb + 1) / 2 : nb * nb;
         constexpr size_t lds = (size_t)2 * XK * XLD * sizeof(float);
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(xty_f64_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            attr_set = true;
-        }
+        hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(xty_f64_kernel), lds);
+        if (e != hipSuccess) return e;
         hipLaunchKernelGGL(xty_f64_kernel, dim3((unsigned)((int64_t)nslab * ntiles)), dim3(256), lds, st, a, ntiles, nb);
         return hipGetLastError();
     }

@@ -455,176 +455,9 @@ __global__ __launch_bounds__(1024) void cholesky_kernel(double* __restrict__ T, 
     }
 }
 
-// Register-resident form for C <= 256: the lower triangle lives in the 1024 threads' registers as 4x4 tiles (two per
-// thread, tile e of the row-major triangle on thread e % 1024) for the whole factorisation.  Per 16-wide
-// panel: its tiles go to LDS, wave 0 factors AND inverts the 16x16 diagonal block, the panel solve is a product with that inverse on the MFMA, every
-// thread applies the rank-16 update to the tiles it owns -- four barriers and no global round trip inside the loop
-// (the form above pays three L2 round trips per panel: measured 190 us at C = 256, of which the flops are ~25).
-#ifndef CHOL_SKIP
-#define CHOL_SKIP 0      // development: 1 no diagonal factor, 2 no panel solve, 4 no update, 8 no extraction (wrong results)
-#endif
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-// Register-resident form for C <= 256: the trailing matrix lives in the 16 waves' registers as 16x16 blocks in the
-// f64-MFMA accumulator layout (register r of lane l = block[(l>>4) + 4r][l&15]) for the whole factorisation (8 waves).  Per
-// 16-wide panel: its blocks go to LDS, wave 0 factors AND inverts the 16x16 diagonal block, the panel solve is a product with that inverse on the MFMA,
-// every wave applies the rank-16 update to its blocks with four v_mfma_f64_16x16x4_f64 each (operands: two doubles
-// per lane and MFMA from the solved panel in LDS) -- four barriers and no global round trip inside the loop.  (The
-// form above pays three L2 round trips per panel and runs the update on 4x4 register micro-tiles fed from LDS.)
-// Blocks are ranked by block column, LAST column first, and dealt to the waves round-robin: the blocks still active
-// at any panel step are a prefix of the ranking, so the waves stay evenly loaded as the matrix shrinks.
-__global__ __launch_bounds__(512) void cholesky_reg_kernel(double* __restrict__ T, int C, int ldp)
-{
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    double* Praw = sm;                  // [C][17]   the panel as its owners hold it (row-major)
-    double* D = Praw + C * 17;          // [16][17]  INVERSE of the factored diagonal block
-    double* rdiag = D + 16 * 17;        // [16]  (unused)
-    double* Pn = rdiag + 16;            // [16][ldp] solved panel, column-major: the update's operands
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // scalar: block ownership stays in SGPRs
-    const int li = lane & 15, lq = lane >> 4;
-    T += (int64_t)blockIdx.x * C * C;   // one matrix (statistic group) per workgroup
-    const int nb = C >> 4;              // block rows; block column 0 (the first panel) goes from global straight to LDS
-    const int nblk = (nb - 1) * nb / 2;
-
-    constexpr int SLOTS = 15;           // 120 blocks at C = 256 over 8 waves (512 threads: 256 VGPRs each, no spills)
-    int bi_[SLOTS], bj_[SLOTS];
-    f64x4 blk[SLOTS];
-#pragma unroll
-    for (int q = 0; q < SLOTS; ++q) {
-        const int r = wave + 8 * q;
-        bi_[q] = -1; bj_[q] = 0;
-        if (r < nblk) {
-            int m = (int)((sqrt(8.0 * (double)r + 1.0) - 1.0) * 0.5);
-            while ((m + 1) * (m + 2) / 2 <= r) ++m;
-            while (m * (m + 1) / 2 > r) --m;                    // column nb-1-m holds m+1 blocks
-            bj_[q] = nb - 1 - m; bi_[q] = bj_[q] + (r - m * (m + 1) / 2);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) blk[q][e] = T[(int64_t)(16 * bi_[q] + lq + 4 * e) * C + 16 * bj_[q] + li];
-        }
-    }
-    for (int e = tid; e < C * 16; e += 512) Praw[(e >> 4) * 17 + (e & 15)] = T[(int64_t)(e >> 4) * C + (e & 15)];
-
-    for (int j = 0; j < nb; ++j) {
-        const int j0 = 16 * j;
-        const int rows = C - j0 - CH_NB;
-        const int g0 = j0 + CH_NB;
-        // (1) the panel's blocks (block column j) leave the registers
-        if (j > 0) {
-#pragma unroll
-            for (int q = 0; q < SLOTS; ++q) {
-                if (bi_[q] >= 0 && bj_[q] == j && !(CHOL_SKIP & 8)) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) Praw[(16 * bi_[q] + lq + 4 * e) * 17 + li] = blk[q][e];
-                }
-            }
-        }
-        __syncthreads();
-        // (2) wave 0 factors the 16x16 diagonal block in registers: lane = row, readlane broadcasts the pivot column;
-        //     the pivot's reciprocal square root comes from v_rsq_f64 + two Newton steps
-        if (wave == 0 && !(CHOL_SKIP & 1)) {
-            double a[CH_NB];
-            double myrd = 1.0;
-#pragma unroll
-            for (int c = 0; c < CH_NB; ++c) a[c] = Praw[(j0 + li) * 17 + c];
-#pragma unroll
-            for (int jj = 0; jj < CH_NB; ++jj) {
-                const double p = readlane64(a[jj], jj);
-                double rd = __builtin_amdgcn_rsq(p);
-                rd = rd * (1.5 - 0.5 * p * rd * rd);
-                rd = rd * (1.5 - 0.5 * p * rd * rd);
-                const double d = p * rd;
-                if (li == jj) myrd = rd;
-                a[jj] = (li == jj) ? d : a[jj] * rd;
-#pragma unroll
-                for (int k = jj + 1; k < CH_NB; ++k) {
-                    const double lkj = readlane64(a[jj], k);
-                    a[k] -= a[jj] * lkj;
-                }
-            }
-            // ... and inverts it: lane = column c of the inverse, forward substitution with the rows of L read by
-            // readlane (the panel solve below is then a product on the MFMA instead of 136 dependent steps per row)
-            double w[CH_NB];
-#pragma unroll
-            for (int i = 0; i < CH_NB; ++i) w[i] = (i == li) ? myrd : 0.0;
-#pragma unroll
-            for (int i = 1; i < CH_NB; ++i) {
-                double acc = 0.0;
-#pragma unroll
-                for (int kk = 0; kk < i; ++kk) acc += readlane64(a[kk], i) * w[kk];
-                const double wi = -acc * readlane64(myrd, i);
-                w[i] = (i > li) ? wi : w[i];
-            }
-            if (lane < 16) {
-#pragma unroll
-                for (int c = 0; c < CH_NB; ++c) {
-                    const double v = (c <= lane) ? a[c] : 0.0;
-                    T[(int64_t)(j0 + lane) * C + j0 + c] = v;
-                }
-#pragma unroll
-                for (int i = 0; i < CH_NB; ++i) D[i * 17 + lane] = w[i];       // D[i][c] = (L^-1)[i][c]
-            }
-        }
-        __syncthreads();
-        if (rows <= 0) break;
-        // (3) panel solve X = P L^-T as a product with the inverted diagonal block: X[r][c] = sum_k P[r][k] Linv[c][k],
-        //     one 16-row block per wave and pass, four f64 MFMAs each
-        if (!(CHOL_SKIP & 2)) {
-            for (int rb = wave; 16 * rb < rows; rb += 8) {
-                const int row0 = g0 + 16 * rb;
-                f64x4 x = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    const double av = Praw[(row0 + li) * 17 + 4 * kk + lq];
-                    const double bv = D[li * 17 + 4 * kk + lq];
-                    x = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, x, 0, 0, 0);
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int r = row0 + lq + 4 * e;
-                    T[(int64_t)r * C + j0 + li] = x[e];
-                    Pn[li * ldp + r] = x[e];
-                }
-            }
-        }
-        __syncthreads();
-        // (4) rank-16 update of the blocks still in registers: block(bi, bj) -= P[bi] P[bj]^T.  The active blocks are a
-        //     prefix of this wave's slots; they are taken three at a time -- all 24 operand reads first, then the three
-        //     independent MFMA chains interleaved -- and a dead block in the last group is simply updated too.
-        int nact = 0;
-#pragma unroll
-        for (int q = 0; q < SLOTS; ++q) nact += (bi_[q] >= 0 && bj_[q] > j) ? 1 : 0;
-        if (CHOL_SKIP & 4) nact = 0;
-#pragma unroll
-        for (int g3 = 0; g3 < SLOTS / 3; ++g3) {
-            if (3 * g3 >= nact) break;
-            double av[3][4], bv[3][4];
-#pragma unroll
-            for (int u = 0; u < 3; ++u) {
-                const int q = 3 * g3 + u;
-                const int bi = bi_[q] >= 0 ? bi_[q] : 0, bj = bi_[q] >= 0 ? bj_[q] : 0;
-                const double* pa = Pn + lq * ldp + 16 * bi + li;
-                const double* pb = Pn + lq * ldp + 16 * bj + li;
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) { av[u][kk] = -pa[4 * kk * ldp]; bv[u][kk] = pb[4 * kk * ldp]; }
-            }
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int u = 0; u < 3; ++u)
-                    blk[3 * g3 + u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u][kk], bv[u][kk], blk[3 * g3 + u], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    // strict upper triangle := 0
-    for (int64_t e = tid; e < (int64_t)C * C; e += 512) {
-        const int i = (int)(e / C), jx = (int)(e % C);
-        if (jx > i) T[e] = 0.0;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // K2 for C <= 256, second form (round 2): ONE launch factors T = L L^T and inverts the 16 x 16 diagonal blocks of
-// L; a second launch builds W = L^-1 column block by column block.  What changed against cholesky_reg_kernel + the
+// L; a second launch builds W = L^-1 column block by column block.  What changed against round 1's cholesky_reg_kernel (since removed) + the
 // seven block-doubling launches below:
 //  * The serial part -- factoring AND inverting the 16 x 16 diagonal block -- runs on DPP row broadcasts
 //    (gfx90a+: v_fmac_f64_dpp / v_mov_b64_dpp with row_newbcast:k read lane k of the 16-lane row, which IS "row k
@@ -849,50 +682,18 @@ __device__ __forceinline__ void tri_inverse_role(const double* __restrict__ L, c
     }
 }
 
-__global__ __launch_bounds__(1024) void tri_inverse_split_kernel(const double* __restrict__ L, const double* __restrict__ Linv,
-                                                                 double* __restrict__ W, int C)
-{
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    tri_inverse_role(L + (int64_t)blockIdx.y * C * C, Linv + (int64_t)blockIdx.y * C * 16, W + (int64_t)blockIdx.y * C * C, C,
-                     (int)blockIdx.x, nullptr, sm);
-}
+constexpr int CF_OWN = 15;          // waves that own trailing blocks and solve the panel: every wave but wave 0.  (12 = all but 4, 8, 12, which share
+                                    // wave 0's SIMD: measured 74 against 69 us -- the early steps are bound by the CU's f64-MFMA rate and lose a quarter of it)
+constexpr int CF_SLOTS = (120 + CF_OWN - 1) / CF_OWN;      // 120 blocks at C = 256 (16 waves x 128 VGPRs: 10 blocks = 80 of them)
 
-#ifndef CF_OWN
-#define CF_OWN 15                   // waves that own trailing blocks and solve the panel.  (12 = all but 4, 8, 12, which share wave 0's
-#endif                              // SIMD: measured 74 against 69 us -- the early steps are bound by the CU's f64-MFMA rate and lose a quarter of it)
-constexpr int CF_SLOTS = (120 + CF_OWN - 1) / CF_OWN;
-// (CF_SPLIT_B counts one s_barrier per step for every wave: the idle-wave form of CF_OWN = 12 keeps two)
-#if CF_OWN != 15 && !defined(CF_SPLIT_B)
-#define CF_SPLIT_B 0
-#endif      // 120 blocks at C = 256 (16 waves x 128 VGPRs: 10 blocks = 80 of them)
-
-#ifndef CF_NEWTON
-#define CF_NEWTON 1        // Newton steps on v_rsq_f64 per pivot (measured: L to 1e-13 with one, 1e-7 with none)
-#endif
-#ifndef CF_SPLIT_B
-#define CF_SPLIT_B 1     // round 4: barrier (B) is a counter among the owner waves only; wave 0 solves the next diagonal block's rows itself and never waits for the panel
-#endif
-#ifndef CF_STAMPS
-#define CF_STAMPS 0      // development: s_memtime stamps around every barrier of waves 0, 1 and 5 into the workspace behind Linv
-#endif
 // LDS hand-off only: every wave's LDS traffic has completed, then the barrier.  (__syncthreads() would also wait for the
 // global stores of L in flight, half a microsecond per step for nothing: nobody reads them inside this launch.)
-#define CF_BARRIER() do { if (CF_STAMPS && stamp_ok) stamps[nstamp++] = __builtin_amdgcn_s_memtime();              \
-                          asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                          \
-                          if (CF_STAMPS && stamp_ok) stamps[nstamp++] = __builtin_amdgcn_s_memtime(); } while (0)
+#define CF_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
-// rows != nullptr: the launch carries TI_WG inverse workgroups per matrix behind the `groups` factorising ones (tri_inverse_role);
-// rows[16 g] counts the complete row blocks of matrix g (zeroed by factor_prepare_kernel)
-__global__ __launch_bounds__(1024) void cholesky_fused_kernel(double* __restrict__ T, double* __restrict__ Linv, int C, int ldp,
-                                                              double* __restrict__ Winv, unsigned* __restrict__ rows, int groups)
+// one workgroup per matrix; W follows in a launch of its own (tri_inverse_cols_kernel)
+__global__ __launch_bounds__(1024) void cholesky_fused_kernel(double* __restrict__ T, double* __restrict__ Linv, int C, int ldp)
 {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    if ((int)blockIdx.x >= groups) {
-        const int idx = (int)blockIdx.x - groups, g = idx / TI_WG;
-        tri_inverse_role(T + (int64_t)g * C * C, Linv + (int64_t)g * C * 16, Winv + (int64_t)g * C * C, C, idx % TI_WG, rows + 16 * g, sm);
-        return;
-    }
-    unsigned* rowflag = rows ? rows + 16 * blockIdx.x : nullptr;
     double* Praw = sm;                          // [2][C][17]  the current / next panel as its owners hold it (row-major)
     double* Pn = Praw + 2 * C * 17;             // [C][17]     solved panel, row-major like Praw: the update's MFMA operands.  (Round 6: it was
                                                 // [16][C + 2] column-major -- lanes (li, lq) and (li + 2, lq - 1) of an operand read met in one bank,
@@ -900,7 +701,7 @@ __global__ __launch_bounds__(1024) void cholesky_fused_kernel(double* __restrict
                                                 // tools/probe/mfma_f64_rate.hip)
     double* Dinv = Pn + C * 17;                 // [2][16][17] INVERSE of the factored diagonal block (even / odd steps)
     double* Dpre = Dinv + 2 * 16 * 17;          // [2][16][17] diagonal block (b, b) with every update but the last one, b even / odd
-    volatile int* const cntB = reinterpret_cast<volatile int*>(Dpre + 2 * 16 * 17);      // CF_SPLIT_B: owner waves through the panel solve (running count)
+    volatile int* const cntB = reinterpret_cast<volatile int*>(Dpre + 2 * 16 * 17);      // barrier (B): owner waves through the panel solve (running count)
     const unsigned cntB_lds = (unsigned)(size_t)((__attribute__((address_space(3))) char*)(Dpre + 2 * 16 * 17));
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -915,10 +716,6 @@ __global__ __launch_bounds__(1024) void cholesky_fused_kernel(double* __restrict
     if (nb > 1)
         for (int e = tid; e < 256; e += 1024) Dpre[16 * 17 + (e >> 4) * 17 + (e & 15)] = T[(int64_t)(16 + (e >> 4)) * C + 16 + (e & 15)];    // block (1,1) as it stands
     __syncthreads();
-    const bool stamp_ok = CF_STAMPS && lane == 0 && blockIdx.x == 0;
-    unsigned long long* stamps = reinterpret_cast<unsigned long long*>(Linv + 8192) + wave * 128;
-    int nstamp = 0;
-    (void)stamps; (void)nstamp; (void)stamp_ok;
 
     // Two barriers per step.  (A): the inverse of L_jj is in LDS and panel j is complete.  (B): panel j is solved.
     // Between (B) and the next (A) wave 0 gives the next diagonal block its last update itself and factors it, while the
@@ -936,12 +733,7 @@ __global__ __launch_bounds__(1024) void cholesky_fused_kernel(double* __restrict
                 constexpr int jj = decltype(J)::value;
                 const double p = row_bcast<jj>(a[jj]);
                 double rd = __builtin_amdgcn_rsq(p);
-#if CF_NEWTON >= 1
                 rd = rd * (1.5 - 0.5 * p * rd * rd);
-#endif
-#if CF_NEWTON >= 2
-                rd = rd * (1.5 - 0.5 * p * rd * rd);
-#endif
                 a[jj] = (li == jj) ? p * rd : a[jj] * rd;
                 dpp_settle(a[jj]);
                 const double nj = -a[jj];
@@ -957,12 +749,6 @@ __global__ __launch_bounds__(1024) void cholesky_fused_kernel(double* __restrict
                 w[jj] = (li == jj) ? rd : (li < jj ? -acc * rd : 0.0);
             });
             double* dv = Dinv + (j & 1) * (16 * 17);
-            if (rowflag) {
-                // row blocks 0..j-1 are complete: the owners' panel stores landed before barrier (A) of step j-1, this wave's
-                // own (the inverse of block j-1) were issued a whole step ago
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if (lane == 0) __hip_atomic_store(rowflag, (unsigned)j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
             if (lane < 16) {
 #pragma unroll
                 for (int c = 0; c < 16; ++c) T[(int64_t)(16 * j + lane) * C + 16 * j + c] = (c <= lane) ? a[c] : 0.0;
@@ -974,18 +760,11 @@ __global__ __launch_bounds__(1024) void cholesky_fused_kernel(double* __restrict
 #pragma unroll 1
         for (int j = 0; j < nb; ++j) {
             CF_BARRIER();                                          // (A)
-            if (C - 16 * (j + 1) <= 0) {
-                if (rowflag) {                                     // the last block's inverse has landed: L is complete
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    if (lane == 0) __hip_atomic_store(rowflag, (unsigned)nb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                break;
-            }
+            if (C - 16 * (j + 1) <= 0) break;
             // the last update of block (j+1, j+1): D -= X X^T with X = rows 16(j+1).. of the solved panel; through LDS into
             // the lane = row layout of the factorisation
             double* dp = Dpre + ((j + 1) & 1) * (16 * 17);
             f64x4 d4, d5 = {0.0, 0.0, 0.0, 0.0};
-#if CF_SPLIT_B
             // Those 16 rows of X are solved HERE as well (the owner of row block 0 publishes them for everybody else): X^T = Linv P^T with
             // the operand roles of the owners' product swapped, same pairs of k-groups in the same order, so register kk of the result is
             // X[li][lq + 4 kk] -- exactly the A (and B) operand of the update below.  Wave 0 then needs nothing the other waves produce
@@ -1007,24 +786,14 @@ __global__ __launch_bounds__(1024) void cholesky_fused_kernel(double* __restrict
                 d4 = __builtin_amdgcn_mfma_f64_16x16x4f64(-xa[2], xa[2], d4, 0, 0, 0);
                 d5 = __builtin_amdgcn_mfma_f64_16x16x4f64(-xa[3], xa[3], d5, 0, 0, 0);
             }
-#else
-            CF_BARRIER();                                          // (B) the others have solved panel j
-            const double* px = Pn + (16 * (j + 1) + li) * 17 + lq;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) d4[r] = dp[(lq + 4 * r) * 17 + li];
-            d4 = __builtin_amdgcn_mfma_f64_16x16x4f64(-px[0], px[0], d4, 0, 0, 0);
-            d5 = __builtin_amdgcn_mfma_f64_16x16x4f64(-px[4], px[4], d5, 0, 0, 0);
-            d4 = __builtin_amdgcn_mfma_f64_16x16x4f64(-px[8], px[8], d4, 0, 0, 0);
-            d5 = __builtin_amdgcn_mfma_f64_16x16x4f64(-px[12], px[12], d5, 0, 0, 0);
-#endif
             d4 += d5;
 #pragma unroll
             for (int r = 0; r < 4; ++r) dp[(lq + 4 * r) * 17 + li] = d4[r];
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // own LDS writes before own reads (one wave: no barrier needed)
             factor(j + 1, dp);
         }
-    } else if (CF_OWN == 15 || (wave & 3) != 0) {
-        const int ow = CF_OWN == 15 ? wave - 1 : wave - 1 - (wave >> 2);        // owner index 0..CF_OWN-1
+    } else {
+        const int ow = wave - 1;                                  // owner index 0..CF_OWN-1
         // the owner waves hold the trailing blocks: ranked by block column, LAST column first, the diagonal block first within a
         // column, dealt round-robin -- the blocks still active at a step are a prefix of every wave's slots.
         // One packed SGPR per slot (bi << 8 | bj), integer arithmetic only.
@@ -1092,9 +861,7 @@ __global__ __launch_bounds__(1024) void cholesky_fused_kernel(double* __restrict
                     }
                 }
             }
-#if CF_SPLIT_B
             {   // (B) among the owners: every owner's rows of the solved panel are in LDS
-                if (CF_STAMPS && stamp_ok) stamps[nstamp++] = __builtin_amdgcn_s_memtime();
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 if (lane == 0) { const unsigned one = 1u; asm volatile("ds_add_u32 %0, %1" :: "v"(cntB_lds), "v"(one) : "memory"); }
                 const int target = CF_OWN * (j + 1);
@@ -1103,11 +870,7 @@ __global__ __launch_bounds__(1024) void cholesky_fused_kernel(double* __restrict
                     asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(cntB_lds) : "memory");
                     if (__builtin_amdgcn_readfirstlane(v) >= target) break;
                 }
-                if (CF_STAMPS && stamp_ok) stamps[nstamp++] = __builtin_amdgcn_s_memtime();
             }
-#else
-            CF_BARRIER();                                          // (B) panel j is solved
-#endif
             // (S4) this wave's active slots are [0, n34): ranks below R4 lie right of the next panel, the next nb-j-1 ranks ARE
             // the next panel (column j+1; rank = owner index + CF_OWN * slot).  The next panel's blocks go first and leave for the other
             // panel buffer -- except the diagonal one, which wave 0 updates and factors itself.  The diagonal block after
@@ -1139,16 +902,6 @@ __global__ __launch_bounds__(1024) void cholesky_fused_kernel(double* __restrict
             cur ^= 1;
         }
     }
-    else {
-        // waves 4, 8, 12: on wave 0's SIMD; they only keep the barrier count
-#pragma unroll 1
-        for (int j = 0; j < nb; ++j) {
-            CF_BARRIER();
-            if (C - 16 * (j + 1) <= 0) break;
-            CF_BARRIER();
-        }
-    }
-    if (CF_STAMPS && stamp_ok) { stamps[nstamp++] = __builtin_amdgcn_s_memtime(); stamps[127] = nstamp; }
     // L's upper triangle: the blocks above the diagonal were zero on entry (factor_prepare_kernel), the diagonal blocks
     // were written whole
 }
@@ -1242,18 +995,13 @@ __device__ __forceinline__ f64x4 cp_load_block_sc1(__amdgpu_buffer_rsrc_t r, int
     return odd ? f64x4{r0, r1, v0[1], v1[1]} : f64x4{v0[0], v1[0], r0, r1};
 }
 
-#ifndef CP_SKIP
-#define CP_SKIP 0        // development ablations (WRONG results): 1 no update MFMAs, 2 no trailing update at all, 4 no panel-solve MFMAs, 8 no pivots in the leaf, 16 no panel stores to global memory
-#endif
-#define CP_BARRIER() do { if (CF_STAMPS && stamp_ok && nstamp < 100) stamps[nstamp++] = __builtin_amdgcn_s_memtime();              \
-                          asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                          \
-                          if (CF_STAMPS && stamp_ok && nstamp < 100) stamps[nstamp++] = __builtin_amdgcn_s_memtime(); } while (0)
+#define CP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 // One factoriser of the relay: active in the steps [jbeg, jend), where it owns the trailing blocks of the block columns [max(jbeg, 1), jend)
 // (rows from the diagonal down to the matrix' last).  Before that it is PASSIVE: it applies the panels 0 .. jbeg-1 to those blocks as the
 // factorisers before it publish them (fetch rows >= 16 jbeg of the solved panel, update).  jbeg = 0: the first one; jend = nb: the last.
 __device__ __forceinline__ void cp_factor_role(double* __restrict__ T, double* __restrict__ Linv, int C, unsigned* sync, int jbeg, int jend,
-                                               double* sm, unsigned long long* stamp_base)
+                                               double* sm)
 {
     double* Praw = sm;                          // [2][C][17]  the current / next panel as its owners hold it (row-major)
     double* Pn = Praw + 2 * C * 17;             // [C][17]     solved panel: the update's MFMA operands
@@ -1269,10 +1017,6 @@ __device__ __forceinline__ void cp_factor_role(double* __restrict__ T, double* _
     const int li = lane & 15, lq = lane >> 4;
     const int nb = C >> 4;
     const __amdgpu_buffer_rsrc_t rT = cp_rsrc(T), rLinv = cp_rsrc(Linv);
-    const bool stamp_ok = CF_STAMPS && lane == 0 && stamp_base != nullptr;
-    unsigned long long* stamps = stamp_base + wave * 128;
-    int nstamp = 0;
-    (void)stamps; (void)nstamp; (void)stamp_ok;
     if (tid == 0) cntB[0] = 0;
     // a passive step's fetch: rows >= 16 jbeg of the solved panel j -> Pn, 16 bytes per thread and load (all 16 waves)
     auto stage_panel = [&](int j) __attribute__((always_inline)) {
@@ -1301,8 +1045,6 @@ __device__ __forceinline__ void cp_factor_role(double* __restrict__ T, double* _
 #pragma unroll
                 for (int c = 0; c < 16; ++c) a[c] = T[(int64_t)(16 * j + li) * C + 16 * j + c];
             }
-            if (CF_STAMPS && stamp_ok) { if (src) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                                         stamps[40 + 5 * (j - jbeg) + 1] = __builtin_amdgcn_s_memtime(); }
             // Round 6 (probe V5: 3 720 -> 3 070 cycles alone on its SIMD): the pivot column is scaled by the raw rsq first and by the Newton
             // factor after (a * rn runs beside the Newton step, not behind it); lane jj's a[jj] IS the pivot, no select; the negation rides
             // on the FMA's source modifier; the next pivot's broadcast is issued behind the first three updates of this one (leaf_head3).
@@ -1313,7 +1055,6 @@ __device__ __forceinline__ void cp_factor_role(double* __restrict__ T, double* _
                          "v_fmac_f64_dpp %1, %2, %4 row_newbcast:0 row_mask:0xf bank_mask:0xf" : "+v"(p), "+v"(hp) : "v"(a[0]), "v"(one), "v"(half));
             static_for<0, 16>([&](auto J) {
                 constexpr int jj = decltype(J)::value;
-                if (CP_SKIP & 8) { w[jj] = a[jj]; return; }
                 const double rn = __builtin_amdgcn_rsq(p);
                 const double t = hp * rn;
                 const double ua = a[jj] * rn;
@@ -1338,7 +1079,6 @@ __device__ __forceinline__ void cp_factor_role(double* __restrict__ T, double* _
                 });
                 w[jj] = -acc * rd;
             });
-            if (CF_STAMPS && stamp_ok) { asm volatile("" :: "v"(a[15]), "v"(w[15])); stamps[40 + 5 * (j - jbeg) + 2] = __builtin_amdgcn_s_memtime(); }
             if (lane < 16) {
                 double* lg = Ldg + (j & 1) * (16 * 18);
                 double* dv = DinvT + (j & 1) * (16 * 18);
@@ -1347,7 +1087,6 @@ __device__ __forceinline__ void cp_factor_role(double* __restrict__ T, double* _
 #pragma unroll
                 for (int i = 0; i < 16; i += 2) *reinterpret_cast<f64x2*>(dv + lane * 18 + i) = f64x2{w[i], w[i + 1]};     // [c][i], zero where i < c
             }
-            if (CF_STAMPS && stamp_ok) stamps[40 + 5 * (j - jbeg) + 3] = __builtin_amdgcn_s_memtime();
         };
         if (jbeg == 0) factor(0, nullptr);
         else {
@@ -1406,7 +1145,6 @@ __device__ __forceinline__ void cp_factor_role(double* __restrict__ T, double* _
 #pragma unroll
             for (int r = 0; r < 4; ++r) dp[(lq + 4 * r) * 18 + li] = d4[r];
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // own LDS writes before own reads (one wave: no barrier needed)
-            if (CF_STAMPS && stamp_ok) stamps[40 + 5 * (j + 1 - jbeg)] = __builtin_amdgcn_s_memtime();
             factor(j + 1, dp);
         }
     } else {
@@ -1460,22 +1198,17 @@ __device__ __forceinline__ void cp_factor_role(double* __restrict__ T, double* _
             static_for<0, CP_SLOTS>([&](auto Q) {
                 constexpr int q = CP_SLOTS - 1 - decltype(Q)::value;
                 if (q < n34) {
-                    if (CF_STAMPS && stamp_ok && j == jbeg) stamps[100 + q] = __builtin_amdgcn_s_memtime();
                     if (q == n34 - 1) fetch(std::integral_constant<int, q>{});
                     if constexpr (q > 0) fetch(std::integral_constant<int, q - 1>{});
                     // (a next-panel slot that holds the diagonal block takes no update here: wave 0 gives it its last one)
                     if (!(q >= n4 && (bc_[q] >> 8) == (bc_[q] & 255))) {
-                        if (CP_SKIP & 1) { blk[q][0] += av[q & 1][0] * bv[q & 1][1] + av[q & 1][2] * bv[q & 1][3] + av[q & 1][1] * bv[q & 1][0] + av[q & 1][3] * bv[q & 1][2]; }
-                        else {
 #pragma unroll
                         for (int kk = 0; kk < 4; ++kk) blk[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[q & 1][kk], bv[q & 1][kk], blk[q], 0, 0, 0);
-                        }
                     }
                     if constexpr (q + 1 < CP_SLOTS) { if (q + 1 < n34) leave(std::integral_constant<int, q + 1>{}); }
                 }
             });
             if (n34 > 0) leave(std::integral_constant<int, 0>{});
-            if (CF_STAMPS && stamp_ok && j == jbeg) { stamps[106] = __builtin_amdgcn_s_memtime(); asm volatile("s_nop 0" :: "v"(blk[0])); stamps[107] = __builtin_amdgcn_s_memtime(); }
         };
         // the diagonal block of step j and its inverse, from wave 0's LDS copies to global memory (off wave 0's chain)
         auto publish_diag = [&](int j) __attribute__((always_inline)) {
@@ -1561,12 +1294,11 @@ __device__ __forceinline__ void cp_factor_role(double* __restrict__ T, double* _
                     f64x4 x = {0.0, 0.0, 0.0, 0.0}, x1 = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
                     for (int kk = 0; kk < 4; kk += 2) {
-                        if (CP_SKIP & 4) { x[kk] += pan[(row0 + li_t) * 17 + 4 * kk + lq_t] * dv[(4 * kk + lq_t) * 18 + li_t]; x1[kk] += pan[(row0 + li_t) * 17 + 4 * kk + 4 + lq_t] * dv[(4 * kk + 4 + lq_t) * 18 + li_t]; continue; }
                         x = __builtin_amdgcn_mfma_f64_16x16x4f64(pan[(row0 + li_t) * 17 + 4 * kk + lq_t], dv[(4 * kk + lq_t) * 18 + li_t], x, 0, 0, 0);
                         x1 = __builtin_amdgcn_mfma_f64_16x16x4f64(pan[(row0 + li_t) * 17 + 4 * kk + 4 + lq_t], dv[(4 * kk + 4 + lq_t) * 18 + li_t], x1, 0, 0, 0);
                     }
                     x += x1;
-                    if (!(CP_SKIP & 16)) cp_store_block_sc1(rT, row0 * C + j0, C, x, li_t, lq_t);      // write-through: the inverse role and the second factoriser read it in this launch
+                    cp_store_block_sc1(rT, row0 * C + j0, C, x, li_t, lq_t);      // write-through: the inverse role and the second factoriser read it in this launch
 #pragma unroll
                     for (int e = 0; e < 4; ++e) Pn[(row0 + lq_t + 4 * e) * 17 + li_t] = x[e];
                 }
@@ -1574,7 +1306,6 @@ __device__ __forceinline__ void cp_factor_role(double* __restrict__ T, double* _
             const bool last = j + 1 >= jend;                        // this factoriser's last panel (rows > 0: not the matrix' last)
             if (last) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the meeting below then says: panel j and diagonal block j are complete in memory
             {   // (B) among the owners: every owner's rows of the solved panel are in LDS
-                if (CF_STAMPS && stamp_ok && nstamp < 100) stamps[nstamp++] = __builtin_amdgcn_s_memtime();
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 if (lane == 0) { const unsigned one = 1u; asm volatile("ds_add_u32 %0, %1" :: "v"(cntB_lds), "v"(one) : "memory"); }
                 const int target = 15 * (++nB);
@@ -1583,7 +1314,6 @@ __device__ __forceinline__ void cp_factor_role(double* __restrict__ T, double* _
                     asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(cntB_lds) : "memory");
                     if (__builtin_amdgcn_readfirstlane(v) >= target) break;
                 }
-                if (CF_STAMPS && stamp_ok && nstamp < 100) stamps[nstamp++] = __builtin_amdgcn_s_memtime();
             }
             if (last) {
                 // hand over: the next factoriser's last passive step waits for this panel; the inverse role for row block j
@@ -1593,10 +1323,9 @@ __device__ __forceinline__ void cp_factor_role(double* __restrict__ T, double* _
                 }
                 break;
             }
-            if (!(CP_SKIP & 2)) trailing(j);
+            trailing(j);
         }
     }
-    if (CF_STAMPS && stamp_ok) { if (nstamp < 100) stamps[nstamp++] = __builtin_amdgcn_s_memtime(); stamps[127] = nstamp; }
 }
 
 // grid: [0, groups) first factorisers, [groups, groups (1 + TI_WG)) inverse, then the factorisers 2 .. nparts of every matrix.
@@ -1615,9 +1344,7 @@ __global__ __launch_bounds__(1024) void cholesky_phased_kernel(double* __restric
     const int g = b < groups ? b : (b - groups * (1 + TI_WG)) % groups;
     const int jbeg = part ? (bounds >> (8 * (part - 1))) & 255 : 0;
     const int jend = part + 1 < nparts ? (bounds >> (8 * part)) & 255 : nb;
-    // (development stamps: 16 x 128 words per factoriser of matrix 0)
-    cp_factor_role(T + (int64_t)g * C * C, Linv + (int64_t)g * C * 16, C, sync + 16 * g, jbeg, jend, sm,
-                   (CF_STAMPS && g == 0) ? reinterpret_cast<unsigned long long*>(Linv + 8192) + part * 16 * 128 : nullptr);
+    cp_factor_role(T + (int64_t)g * C * C, Linv + (int64_t)g * C * 16, C, sync + 16 * g, jbeg, jend, sm);
 }
 
 // W = L^-1 from L and the inverses of its 16 x 16 diagonal blocks, one WAVE per block column j:
@@ -1689,19 +1416,13 @@ __global__ __launch_bounds__(512) void tri_inverse_cols_kernel(const double* __r
         if (i + 1 < nb) stash(i + 1);
         if (i + 2 < nb) fetch(i + 2);
     };
-    const bool stamp_ok = CF_STAMPS && lane == 0 && blockIdx.x == 0 && blockIdx.y == 0 && (wave == 0 || wave == 4);
-    unsigned long long* stamps = reinterpret_cast<unsigned long long*>(W + (int64_t)C * C) + (wave == 0 ? 0 : 128);   // (the workspace behind W: development builds only)
-    int nstamp = 0;
-    (void)stamps; (void)nstamp; (void)stamp_ok;
-#define TI_STAMP() do { if (CF_STAMPS && stamp_ok) stamps[nstamp++] = __builtin_amdgcn_s_memtime(); } while (0)
-    auto tail = [&]() { TI_STAMP(); asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); TI_STAMP(); };
+    auto tail = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
     for (int i = 1; i <= j && i < nb; ++i) { head(i); tail(); }                 // steps before this column starts
     static_for<1, 16>([&](auto D) {
         constexpr int d = decltype(D)::value;
         const int i = j + d;
         if (i < nb) {
             head(i);
-            TI_STAMP();
             const double* lr = Lrow + (i & 1) * 16 * ldr + li * ldr + lq + 16 * j;
             // the A operands of product e+1 are read from LDS before the MFMAs of product e issue
             f64x4 S = {0.0, 0.0, 0.0, 0.0}, S1 = {0.0, 0.0, 0.0, 0.0};
@@ -1733,7 +1454,6 @@ __global__ __launch_bounds__(512) void tri_inverse_cols_kernel(const double* __r
             }
             Xi += Xi1;
             X[d] = Xi;
-            TI_STAMP();
             tail();
         }
     });
@@ -1743,8 +1463,6 @@ __global__ __launch_bounds__(512) void tri_inverse_cols_kernel(const double* __r
         constexpr int d = decltype(D)::value;
         if (j + d < nb) store(j + d, X[d]);
     });
-    if (CF_STAMPS && stamp_ok) stamps[127] = nstamp;
-#undef TI_STAMP
 }
 
 // inverse of each 32 x 32 diagonal block of L (lower): one wave per block, lane = column of the inverse
@@ -2049,11 +1767,7 @@ hipError_t wc_launch_bwd_combine(const double* P, const float* colsum, const int
 }
 
 // C <= 256: Cholesky with look-ahead + the inverses of the diagonal blocks in one launch, W in a second one
-static bool use_fused_factor(int C)
-{
-    static const bool off = getenv("WC_CHOL_OLD") != nullptr;             // development: the round-1 kernels
-    return C <= 256 && !off;
-}
+static bool use_fused_factor(int C) { return C <= 256; }
 // factor and inverse in ONE launch (tri_inverse_role): every workgroup of the launch has to be resident at once (the inverse
 // workgroups spin on the factorising ones), so only for a handful of matrices.  Measured on MI355X (tools/k2_pipe_check.py), K2
 // per call, two launches -> one: C = 256: 94.4 -> 73.1 us (5 groups 96.1 -> 76.5, 8 groups 99.0 -> 77.7), C = 224 (3 groups):
@@ -2061,7 +1775,7 @@ static bool use_fused_factor(int C)
 // factorisation's step and two launches are faster (C = 64: 18.9 against 24-30 us).
 static bool factor_one_launch(int C, int groups)
 {
-    static const bool off = getenv("WC_K2_TWO_LAUNCH") != nullptr || getenv("WC_K2_SPLIT") != nullptr;
+    static const bool off = getenv("WC_K2_TWO_LAUNCH") != nullptr;
     return use_fused_factor(C) && C >= 128 && !off && groups * (1 + TI_WG) <= 40;
 }
 
@@ -2098,63 +1812,39 @@ hipError_t wc_launch_stats_prepare(const double* P, const float* colsum, const f
 hipError_t wc_launch_factor_fused(double* T, double* W, double* tmp, int C, int groups, hipStream_t st)
 {
     const int nb = C >> 4, ldp = 17;
-    size_t lds = (size_t)(2 * C * 17 + C * 17 + 4 * 16 * 17 + 2) * sizeof(double);      // (+ the owners' panel counter)
-    const bool one = factor_one_launch(C, groups);
-    static const bool split = getenv("WC_K2_SPLIT") != nullptr;         // development: the four-waves-per-column inverse as a launch of its own
-    const size_t lds_role = ti_role_lds_doubles(C) * sizeof(double);
-    if (one && lds_role > lds) lds = lds_role;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cholesky_fused_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (one) {
+    hipError_t e;
+    if (factor_one_launch(C, groups)) {
+        // the relay's stages.  Every C the one-launch gate admits fits its owners' slots (CP_MAXB) and the passive fetch: the largest
+        // phase is 28 / 45 / 66 blocks at C = 128 / 160 / 192 (one stage), 38 / 50 at C = 224 / 256 (three stages).  The one-stage
+        // retry and the error below are guards that cannot be reached through the gate.
         unsigned* rows = reinterpret_cast<unsigned*>(tmp + (size_t)groups * C * 16);     // zeroed by factor_prepare_kernel
-        static const bool old_one = getenv("WC_K2_FUSED_R5") != nullptr;     // development A/B: round 5's one-workgroup factorisation
-        if (!old_one) {
-            // the relay's stages: WC_K2_BOUNDS="4,9" (development) or the rule below; a stage that does not fit its owners' slots or the
-            // passive fetch -> one stage (or round 5's kernel when even that does not fit)
-            static const char* benv = getenv("WC_K2_BOUNDS");
-            int bnd[4] = {0, 0, 0, 0}, np = 1;
-            if (benv && *benv) {
-                const char* q = benv;
-                while (*q && np < 4) { const int v = atoi(q); if (v > bnd[np - 1] && v < nb) bnd[np++] = v; while (*q && *q != ',') ++q; if (*q == ',') ++q; }
-            } else if (nb >= 14) { bnd[1] = nb / 4; bnd[2] = nb * 9 / 16; np = 3; }
-            bool fits = true;
-            for (int k = 0; k < np; ++k) {
-                const int jb = bnd[k], je = k + 1 < np ? bnd[k + 1] : nb;
-                if (cp_colblocks(jb ? jb : 1, je, nb) > CP_MAXB || (jb && (nb - jb) * 128 > 2048)) fits = false;
-            }
-            if (!fits) { np = 1; fits = cp_colblocks(1, nb, nb) <= CP_MAXB; }
-            if (fits) {
-                size_t l2 = cp_factor_lds_doubles(C) * sizeof(double);
-                if (lds_role > l2) l2 = lds_role;
-                static size_t l2_set = 0;        // (once per size: the attribute call is not free, and not needed again)
-                if (l2 > l2_set) {
-                    e = hipFuncSetAttribute(reinterpret_cast<const void*>(cholesky_phased_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
-                    if (e != hipSuccess) return e;
-                    l2_set = l2;
-                }
-                const int nwg = groups * (np + TI_WG);
-                hipLaunchKernelGGL(cholesky_phased_kernel, dim3(nwg), dim3(1024), l2, st, T, tmp, C, W, rows, groups, np, bnd[1] | (bnd[2] << 8) | (bnd[3] << 16));
-                return hipGetLastError();
-            }
+        int bnd[4] = {0, 0, 0, 0}, np = 1;
+        if (nb >= 14) { bnd[1] = nb / 4; bnd[2] = nb * 9 / 16; np = 3; }
+        bool fits = true;
+        for (int k = 0; k < np; ++k) {
+            const int jb = bnd[k], je = k + 1 < np ? bnd[k + 1] : nb;
+            if (cp_colblocks(jb ? jb : 1, je, nb) > CP_MAXB || (jb && (nb - jb) * 128 > 2048)) fits = false;
         }
-        hipLaunchKernelGGL(cholesky_fused_kernel, dim3(groups * (1 + TI_WG)), dim3(1024), lds, st, T, tmp, C, ldp, W, rows, groups);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(cholesky_fused_kernel, dim3(groups), dim3(1024), lds, st, T, tmp, C, ldp, W, (unsigned*)nullptr, groups);
-    if (split) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(tri_inverse_split_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_role);
+        if (!fits) { np = 1; fits = cp_colblocks(1, nb, nb) <= CP_MAXB; }
+        if (!fits) return hipErrorInvalidValue;
+        size_t lds = cp_factor_lds_doubles(C) * sizeof(double);
+        const size_t lds_role = ti_role_lds_doubles(C) * sizeof(double);
+        if (lds_role > lds) lds = lds_role;
+        e = wc_set_max_lds(reinterpret_cast<const void*>(cholesky_phased_kernel), lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(tri_inverse_split_kernel, dim3(TI_WG, groups), dim3(1024), lds_role, st, (const double*)T, (const double*)tmp, W, C);
+        hipLaunchKernelGGL(cholesky_phased_kernel, dim3(groups * (np + TI_WG)), dim3(1024), lds, st, T, tmp, C, W, rows, groups, np,
+                           bnd[1] | (bnd[2] << 8) | (bnd[3] << 16));
         return hipGetLastError();
     }
+    const size_t lds = (size_t)(2 * C * 17 + C * 17 + 4 * 16 * 17 + 2) * sizeof(double);      // (+ the owners' panel counter)
+    e = wc_set_max_lds(reinterpret_cast<const void*>(cholesky_fused_kernel), lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(cholesky_fused_kernel, dim3(groups), dim3(1024), lds, st, T, tmp, C, ldp);
     const int nwg = ((nb >> 1) + 3) / 4;
     const size_t lds2 = (size_t)(2 * 16 * (C + 2) + nb * 16 * 17) * sizeof(double);
 #define WC_TI_LAUNCH(PER_)                                                                                             \
     do {                                                                                                                \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(tri_inverse_cols_kernel<PER_>),                           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);                                 \
+        e = wc_set_max_lds(reinterpret_cast<const void*>(tri_inverse_cols_kernel<PER_>), lds2);                        \
         if (e != hipSuccess) return e;                                                                                  \
         hipLaunchKernelGGL((tri_inverse_cols_kernel<PER_>), dim3(nwg, groups), dim3(512), lds2, st, (const double*)T,   \
                            (const double*)tmp, W, C);                                                                   \
@@ -2173,23 +1863,12 @@ bool wc_factor_is_fused(int C) { return use_fused_factor(C); }
 
 hipError_t wc_launch_cholesky(double* T, int C, int groups, hipStream_t st)
 {
-    static const bool no_reg = getenv("WC_CHOL_GLOBAL") != nullptr;      // development: the global-memory form
-    if (C <= 256 && !no_reg) {
-        const int ldr = C + 2;
-        const size_t ldsr = (size_t)(C * 17 + 16 * 17 + 16 + 16 * ldr) * sizeof(double);
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cholesky_reg_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(cholesky_reg_kernel, dim3(groups), dim3(512), ldsr, st, T, C, ldr);
-        return hipGetLastError();
-    }
     int ldp = C - CH_NB;
     if (ldp < 4) ldp = 4;
     ldp = (ldp + 3) / 4 * 4;
     const size_t lds = (size_t)(16 * 17 + 16 + 16 * ldp) * sizeof(double);
     if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cholesky_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(cholesky_kernel), lds);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(cholesky_kernel, dim3(groups), dim3(1024), lds, st, T, C, ldp);

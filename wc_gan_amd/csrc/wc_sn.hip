@@ -13,10 +13,7 @@
 namespace {
 
 constexpr int SN_THREADS = 256;
-#ifndef SN_MAXWG_
-#define SN_MAXWG_ 128
-#endif
-constexpr int SN_MAXWG = SN_MAXWG_;      // workgroups per weight (32 until round 2: a 1024 x 9216 critic weight of the Tiny-ImageNet recipe then streamed through 32 CUs)
+constexpr int SN_MAXWG = 128;      // workgroups per weight (32 until round 2: a 1024 x 9216 critic weight of the Tiny-ImageNet recipe then streamed through 32 CUs)
 
 struct SnArgs {
     const float* W; int R, K;
@@ -278,8 +275,7 @@ hipError_t wc_launch_spectral_norm(const float* W, int R, int K, float* u, float
 {
     const size_t lds = wc_sn_lds_bytes(R, K);
     if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sn_forward_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(sn_forward_kernel), lds);
         if (e != hipSuccess) return e;
     }
     float* t = static_cast<float*>(ws);
@@ -318,8 +314,7 @@ hipError_t wc_launch_spectral_norm_batched(const WcSnItem* items, int count, int
     static size_t cap_lds = ~(size_t)0; static int cap = 0;
     if (cap_lds != lds_all) {
         if (lds_all > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sn_forward_batched_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_all);
+            hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(sn_forward_batched_kernel), lds_all);
             if (e != hipSuccess) return e;
         }
         cap = sn_resident_capacity(sn_forward_batched_kernel, lds_all); cap_lds = lds_all;
@@ -348,8 +343,7 @@ hipError_t wc_launch_spectral_norm_batched(const WcSnItem* items, int count, int
         }
         q.first[q.count] = blocks;
         if (lds > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sn_forward_batched_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(sn_forward_batched_kernel), lds);
             if (e != hipSuccess) return e;
         }
         hipLaunchKernelGGL(sn_forward_batched_kernel, dim3(blocks), dim3(SN_THREADS), lds, st, q);

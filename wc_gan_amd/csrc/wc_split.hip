@@ -36,42 +36,9 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#ifndef WC_SPLIT_NT_STORE
-#define WC_SPLIT_NT_STORE 1
-#endif
-#ifndef WC_SPLIT_STAGGER
-#define WC_SPLIT_STAGGER 1
-#endif
-#ifndef WC_SPLIT_STAMPS
-#define WC_SPLIT_STAMPS 0
-#endif
-#ifndef WC_SPLIT_PUB_GAP
-#define WC_SPLIT_PUB_GAP 2      // MFMA gap of a tile's loop in which the next tile's pieces are waited for and published
-#endif
-#ifndef WC_SPLIT_DMA_STEP
-#define WC_SPLIT_DMA_STEP -1    // k-step whose first gap carries the DMAs of tile t+3 (-1: step 1)
-#endif
-#ifndef WC_SPLIT_POLL_SLEEP
-#define WC_SPLIT_POLL_SLEEP 1
-#endif
-#ifndef WC_SPLIT_DEFER
-#define WC_SPLIT_DEFER 0        // 1: a tile's stores ride in the next tile's MFMA gaps; 0: they follow the tile's own loop
-#endif
-#ifndef WC_SPLIT_PRE3
-#define WC_SPLIT_PRE3 0     // 1 (one table for the launch, >= 6 tiles): tile 3's pieces are requested in the prologue with tiles 0-2 (its buffer is free from the start)
-#endif                      // instead of from tile 0's k-step 1, which waits for the table's first fragments: 128 instead of 96 KiB per CU in flight while the table arrives
-#ifndef WC_SPLIT_D0FIRST
-#define WC_SPLIT_D0FIRST 0
-#endif
-#ifndef WC_SPLIT_TROT
-#define WC_SPLIT_TROT 0
-#endif
-#ifndef WC_SPLIT_ABL
-#define WC_SPLIT_ABL 0       // development ablation bits (wrong results, times only; tools/k3_ablations.py): 1 no stores (the hand-counted waits
-                             // adjusted: the DMA waits stay real), 2 no MFMA, 4 linear (unswizzled) DMA source, 8 no table loads (a zero table),
-                             // 16 no mask words (bits not formed, not stored).  (A bit that skipped the epilogue arithmetic HUNG the GPU: the column
-                             // constants arrive by asm loads, and registers nobody reads are handed out again while those loads are in flight.)
-#endif
+constexpr int WC_SPLIT_PUB_GAP = 2;      // MFMA gap of a tile's loop in which the next tile's pieces are waited for and published
+constexpr int WC_SPLIT_DMA_STEP = 1;     // k-step whose first gap carries the DMAs of tile t+3
+constexpr int WC_SPLIT_POLL_SLEEP = 1;   // s_sleep argument of the table poll
 
 namespace {
 
@@ -198,15 +165,11 @@ __global__ __launch_bounds__(512, 1) void apply_split_kernel(SplitApplyArgs a)
     constexpr int ROWB = C * 2, IMG = TR * ROWB, TILE = 2 * IMG;
     constexpr int NBUF = 4;
     static_assert(C == 128 || C == 256, "split apply: C = 128 or 256");
-    static_assert(!(PL && WC_SPLIT_DEFER), "the planes-out epilogue has no deferred-store form (its pend[] / pend_po stay unset)");
     extern __shared__ __attribute__((aligned(1024))) char smem[];      // 4 tiles [hi image | lo image] | counter
     const unsigned tiles_lds = (unsigned)(size_t)((__attribute__((address_space(3))) char*)smem);
     const unsigned cnt_lds = tiles_lds + NBUF * TILE;
     volatile int* const cnt = reinterpret_cast<volatile int*>(smem + NBUF * TILE);
 
-    unsigned long long rt_in = 0;
-    unsigned long long pro_[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // WC_SPLIT_STAMPS: the prologue and tile 0, s_memtime
-    if (WC_SPLIT_STAMPS) rt_in = __builtin_amdgcn_s_memrealtime();
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int cg = wave % CG, rg = wave / CG;
@@ -255,7 +218,7 @@ __global__ __launch_bounds__(512, 1) void apply_split_kernel(SplitApplyArgs a)
     for (int i = 0; i < 4; ++i) {
         const int o = ((4 * wave + i) & 15) * 1024 + 16 * lane;
         const int row = o / ROWB, p = (o % ROWB) >> 4;
-        src_off[i] = (WC_SPLIT_ABL & 4) ? (unsigned)o : (unsigned)(row * ROWB + ((p ^ (row & 15)) << 4));
+        src_off[i] = (unsigned)(row * ROWB + ((p ^ (row & 15)) << 4));
     }
     const char* const plane_base = reinterpret_cast<const char*>(a.xs) + (int64_t)(wave >> 2) * a.plane * 2;
     auto dma_tile = [&](int tl) {
@@ -286,7 +249,7 @@ __global__ __launch_bounds__(512, 1) void apply_split_kernel(SplitApplyArgs a)
             int v;
             asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
             if (__builtin_amdgcn_readfirstlane(v) >= target) break;
-            if (WC_SPLIT_POLL_SLEEP) __builtin_amdgcn_s_sleep(WC_SPLIT_POLL_SLEEP);
+            __builtin_amdgcn_s_sleep(WC_SPLIT_POLL_SLEEP);
         }
     };
 
@@ -303,12 +266,6 @@ __global__ __launch_bounds__(512, 1) void apply_split_kernel(SplitApplyArgs a)
     // the lesson of DESIGN.md section 4.9b again).  So with slots the loads are plain loads hipcc tracks itself, drained at once.
     constexpr bool ASYNC_TABLE = !HAS_SLOT;
     auto load_b = [&](int slot) {
-        if (WC_SPLIT_ABL & 8) {
-#pragma unroll
-            for (int s = 0; s < KS; ++s) { bhi[s] = f16x8{0, 0, 0, 0, 0, 0, 0, 0}; blo[s] = bhi[s]; }
-            cscale[0] = cscale[1] = 1.f; addv[0] = addv[1] = 0.f; cur_slot = slot;
-            return;
-        }
         const char* ph = reinterpret_cast<const char*>(a.Bhi + (int64_t)slot * a.slot_stride + (int64_t)cg * KS * 512);
         const char* pl = reinterpret_cast<const char*>(a.Blo + (int64_t)slot * a.slot_stride + (int64_t)cg * KS * 512);
         const char* pc = reinterpret_cast<const char*>(a.colscale + (a.slot_stride ? (int64_t)slot * C : 0));
@@ -325,12 +282,7 @@ __global__ __launch_bounds__(512, 1) void apply_split_kernel(SplitApplyArgs a)
             cur_slot = slot;
             return;
         }
-#if WC_SPLIT_TROT        // development (WRONG results, times only): every workgroup walks the table from a different k-step -- do 256 CUs reading the same
-        // lines in the same order at the same moment queue up at the same L2 channels?
-        const int rot = (int)((blockIdx.x * 5u) & (unsigned)(KS - 1));
-#else
         const int rot = 0;
-#endif
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
             asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=v"(bhi[s]) : "v"(tb_lane), "s"(ph + 1024 * ((s + rot) & (KS - 1))) : "memory");
@@ -358,26 +310,16 @@ __global__ __launch_bounds__(512, 1) void apply_split_kernel(SplitApplyArgs a)
     // (every wave waits for the same "tile landed" event), so the matrix pipe idled through 1 500 of every 4 600 cycles
     // while both were storing.  Fewer tiles (the small sites): everything drains per tile, stores at the end of the tile.
     const bool def_mode = n >= 6;
-    if (WC_SPLIT_STAMPS) pro_[0] = __builtin_amdgcn_s_memtime();      // in front of the first vector-memory instruction
     if (!ASYNC_TABLE) load_b(a.slot[((int64_t)tile_of(0) * TR) / a.HW]);      // (drained: in front of the DMAs, whose counts start here)
     dma_tile(0);
-#if WC_SPLIT_D0FIRST
-    // Round 6 (stamps, profiles/r6_k3_prologue_stamps.txt): with the table's 36 loads per wave queued right behind D0, a wave's pieces of
-    // tile 0 land 8 000 cycles after its first vector-memory instruction -- 4 300 without the table: 256 KiB per workgroup share the CU's
-    // 64 B/clk return path with the 32 KiB everybody is waiting for.  Tile 0 alone first, the table behind it.
-    if (ASYNC_TABLE && def_mode) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     if (ASYNC_TABLE) load_b(0);
     if (n > 1) dma_tile(1);
     if (n > 2) dma_tile(2);
-    constexpr bool PRE3 = WC_SPLIT_PRE3 && ASYNC_TABLE && !(WC_SPLIT_ABL & 8);
-    if (PRE3 && def_mode) dma_tile(3);             // (def_mode: n >= 6)
-    if (def_mode && ASYNC_TABLE) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(((WC_SPLIT_ABL & 8) ? 0 : 2 * KS + 4) + 8 + (PRE3 ? 4 : 0)) : "memory");      // tile 0 only
+    if (def_mode && ASYNC_TABLE) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * KS + 4 + 8) : "memory");      // tile 0 only
     else if (n > 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else if (n > 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     touch_b();                                    // (unconditional: a tie in one branch only doubles the table's registers at the merge)
-    if (WC_SPLIT_STAMPS) pro_[1] = __builtin_amdgcn_s_memtime();      // my pieces of tile 0 have landed
     arrive(0);                                    // my pieces of tile 0
 
     const int rbase = rg * 32;
@@ -391,11 +333,10 @@ __global__ __launch_bounds__(512, 1) void apply_split_kernel(SplitApplyArgs a)
     const unsigned pl_b = (unsigned)((rbase + 8 * lh + 4 * (l31 & 1)) * C + cg * 32 + (l31 & ~1)) * 2u;
     const unsigned pl_sel = (l31 & 1) ? 0x03020706u : 0x05040100u;       // v_perm_b32(neighbour, own, sel)
     const unsigned mk_b = (unsigned)(cg * 32 + l31) * 4u;                // mask word of column l31 (lanes 0-31 store)
-    if (WC_SPLIT_STAGGER && wave >= 4 && n >= 4) __builtin_amdgcn_s_sleep(24);      // ~a quarter of a tile behind waves 0-3
+    if (wave >= 4 && n >= 4) __builtin_amdgcn_s_sleep(24);      // ~a quarter of a tile behind waves 0-3
 
-    unsigned long long t_wait = 0, t_loop = 0, t_store = 0;
     constexpr int G = 12 * KS32;                               // MFMAs = issue gaps per tile
-    constexpr int DSTEP = WC_SPLIT_DMA_STEP < 0 ? 1 : WC_SPLIT_DMA_STEP;      // k-step whose first gap carries the DMAs of tile t+3
+    constexpr int DSTEP = WC_SPLIT_DMA_STEP;
     constexpr int SG0 = 12 * DSTEP + 2, SGS = (G - SG0 - 1) / 16;             // gaps of the parked stores: SG0 + SGS j, all behind the DMAs
     static_assert(SGS >= 1 && WC_SPLIT_PUB_GAP < 12 * DSTEP, "publication, then DMAs, then stores");
     float pend[16];                                // the previous tile's outputs (scaled, activated, swapped), parked
@@ -406,35 +347,21 @@ __global__ __launch_bounds__(512, 1) void apply_split_kernel(SplitApplyArgs a)
         // value i of a tile: row 16 (i / 8) + (i / 2) % 4 + 4 (i % 2) of the wave's 32 (lanes 32-63: 8 rows below), column l31
         const unsigned olb = ol_b + 0u;            // (an asm operand alone does not capture a variable in a nested generic lambda)
         const float* p = base + (16 * (i >> 3) + ((i >> 1) & 3) + 4 * (i & 1)) * C;
-#if (WC_SPLIT_ABL & 1)
-        asm volatile("" :: "v"(olb), "v"(v), "s"(p));
-#elif WC_SPLIT_NT_STORE
         asm volatile("s_nop 4\n\tglobal_store_dword %0, %1, %2 nt" :: "v"(olb), "v"(v), "s"(p) : "memory");
-#else
-        asm volatile("s_nop 4\n\tglobal_store_dword %0, %1, %2" :: "v"(olb), "v"(v), "s"(p) : "memory");
-#endif
     };
     auto store_u32 = [&](const void* base, unsigned off, unsigned v) __attribute__((always_inline)) {      // plain store (planes, mask): the L2 pairs the 64-byte halves of a line
-#if (WC_SPLIT_ABL & 1)
-        asm volatile("" :: "v"(off), "v"(v), "s"(base));
-#else
         asm volatile("s_nop 4\n\tglobal_store_dword %0, %1, %2" :: "v"(off), "v"(v), "s"(base) : "memory");
-#endif
     };
     // PUB_: the hand-counted vmcnt in front of the publication of tile t+1 (-1: no next tile); DMA_: tile t+3 exists;
     // FIRST_: tile 0 in DEF mode (table k-step by k-step); PEND_: the previous tile's stores ride in this loop; DEFER_: this
     // tile's outputs are parked for the next loop
     auto tile_body = [&](int t, auto pub_tag, auto dma_tag, auto first_tag, auto pend_tag, auto defer_tag) {
-        constexpr int PUB_ = (WC_SPLIT_ABL & 1) && decltype(pub_tag)::value > 0 ? decltype(pub_tag)::value % 16 : decltype(pub_tag)::value;      // (no stores: the counts without the 16 per tile)
+        constexpr int PUB_ = decltype(pub_tag)::value;
         constexpr bool DMA_ = decltype(dma_tag)::value;
         constexpr bool FIRST_ = decltype(first_tag)::value;
         constexpr bool PEND_ = decltype(pend_tag)::value;
         constexpr bool DEFER_ = decltype(defer_tag)::value;
-        unsigned long long c0_ = 0;
-        if (WC_SPLIT_STAMPS) c0_ = __builtin_amdgcn_s_memtime();
         wait_for(0, 8 * (t + 1));                  // tile t has landed for all eight waves
-        unsigned long long c1_ = 0;
-        if (WC_SPLIT_STAMPS) { c1_ = __builtin_amdgcn_s_memtime(); t_wait += c1_ - c0_; if (FIRST_) pro_[2] = c1_; if (t == 1) pro_[6] = c1_; if (t == 2) pro_[7] = c1_; }
         int rb[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) rb[j] = rd_base[j];
@@ -456,16 +383,14 @@ __global__ __launch_bounds__(512, 1) void apply_split_kernel(SplitApplyArgs a)
             if (FIRST_) {    // this k-step's four table fragments have landed (younger: the later k-steps', the 4 column constants, the
                 // DMAs of tiles 1 and 2 and, behind step DSTEP, of tile 3).  No "+v" ties: redefining 128 table registers inside one
                 // of the tile bodies cost 60 VGPRs and spills; the scheduling barrier keeps the k-step's MFMAs behind the wait
-                asm volatile("s_waitcnt vmcnt(%0)" :: "n"(12 + 4 * (KS32 - 1 - s) + ((PRE3 || s > DSTEP) ? 4 : 0)) : "memory");
-                if (WC_SPLIT_STAMPS && (s == 0 || s == KS32 - 1)) pro_[s == 0 ? 3 : 4] = __builtin_amdgcn_s_memtime();      // table k-step 0 / the last one has landed
+                asm volatile("s_waitcnt vmcnt(%0)" :: "n"(12 + 4 * (KS32 - 1 - s) + (s > DSTEP ? 4 : 0)) : "memory");
                 __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
             for (int m = 0; m < 12; ++m) {
                 const int g = 12 * s + m;
                 const int rh = (m >> 1) & 1, ch = m & 1, u = 2 * s + ch, pr = m >> 2;
-                if (WC_SPLIT_ABL & 2) { asm volatile("" :: "v"(ah[rh]), "v"(al[rh]), "v"(bhi[u]), "v"(blo[u])); }
-                else if (pr == 0) acc[rh][ch] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[rh], bhi[u], acc[rh][ch], 0, 0, 0);
+                if (pr == 0) acc[rh][ch] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[rh], bhi[u], acc[rh][ch], 0, 0, 0);
                 else if (pr == 1) acc[rh][ch] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rh], blo[u], acc[rh][ch], 0, 0, 0);
                 else acc[rh][ch] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rh], bhi[u], acc[rh][ch], 0, 0, 0);
                 if (s + 1 < KS32) {
@@ -476,7 +401,6 @@ __global__ __launch_bounds__(512, 1) void apply_split_kernel(SplitApplyArgs a)
                 }
                 if (PUB_ >= 0 && g == (FIRST_ ? G - 6 : WC_SPLIT_PUB_GAP)) {      // my pieces of tile t+1 have landed: publish (tile 0: behind the table)
                     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PUB_) : "memory");
-                    if (WC_SPLIT_STAMPS && FIRST_) pro_[5] = __builtin_amdgcn_s_memtime();      // my pieces of tile 1 have landed (waited for behind the table)
                     arrive(0);
                 }
                 if (DMA_ && g == 12 * DSTEP) {      // tile t-1 read by all: its buffer takes tile t+3
@@ -491,8 +415,6 @@ __global__ __launch_bounds__(512, 1) void apply_split_kernel(SplitApplyArgs a)
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         arrive(1 + (t & (NBUF - 1)));              // my reads of tile t have returned
-        unsigned long long c2_ = 0;
-        if (WC_SPLIT_STAMPS) { c2_ = __builtin_amdgcn_s_memtime(); t_loop += c2_ - c1_; }
         // epilogue (affine_ring_kernel's): scale, bias, activation; v_permlane16_swap of the two column halves' registers gives
         // 2 rows x 32 columns per register -- 128-byte row pieces.  Stores: SGPR row base + one lane offset.
         int tq = t;
@@ -518,7 +440,7 @@ __global__ __launch_bounds__(512, 1) void apply_split_kernel(SplitApplyArgs a)
                     v1 = !(v1 <= 0.f) ? v1 : 0.f;
                 }
                 asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(v0), "+v"(v1));
-                if (MASK && !(WC_SPLIT_ABL & 16)) {      // after the ReLU a value is +0 or passes: v0 is row 16 rh + r (+ 8 in lanes 32-63), v1 four rows below; column l31
+                if (MASK) {      // after the ReLU a value is +0 or passes: v0 is row 16 rh + r (+ 8 in lanes 32-63), v1 four rows below; column l31
                     const unsigned b0 = __builtin_bit_cast(unsigned, v0), b1 = __builtin_bit_cast(unsigned, v1);
                     bits |= (b0 < 1u ? b0 : 1u) << (16 * rh + r);
                     bits |= (b1 < 1u ? b1 : 1u) << (16 * rh + r + 4);
@@ -557,7 +479,7 @@ __global__ __launch_bounds__(512, 1) void apply_split_kernel(SplitApplyArgs a)
 #pragma unroll
             for (int i = 0; i < 16; ++i) store_pair(po, i, res[i]);
         }
-        if (MASK && !(WC_SPLIT_ABL & 16)) {
+        if (MASK) {
             // lanes l and l + 32 hold the two halves of column l31's 32 row bits (rows +0..7, +16..23 | +8..15, +24..31); one more
             // store per tile than the schedule's count of 16: a hand-counted wait only gets more conservative by it
             unsigned own = bits, other = bits;
@@ -566,7 +488,6 @@ __global__ __launch_bounds__(512, 1) void apply_split_kernel(SplitApplyArgs a)
             const unsigned word = own | (other << 8);
             if (lh == 0) store_u32(pm, mk_b, word);
         }
-        if (WC_SPLIT_STAMPS) t_store += __builtin_amdgcn_s_memtime() - c2_;
     };
     using N_ = std::integral_constant<int, -1>;
     using P0 = std::integral_constant<int, 0>; using P4 = std::integral_constant<int, 4>; using P8 = std::integral_constant<int, 8>;
@@ -578,8 +499,6 @@ __global__ __launch_bounds__(512, 1) void apply_split_kernel(SplitApplyArgs a)
             if (slot != cur_slot) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); load_b(slot); touch_b(); }      // (load_b drains: plain loads with slots)
         }
     };
-    unsigned long long k0_ = 0, rt_loop = 0;
-    if (WC_SPLIT_STAMPS) { k0_ = __builtin_amdgcn_s_memtime(); rt_loop = __builtin_amdgcn_s_memrealtime(); }
     // The vector-memory operations of a wave in issue order (DEF): D0, table, D1, D2 | tile 0: D3 | tile 1: D4, S0 | tile 2: D5, S1 |
     // ... | tile t: D(t+3) if it exists, S(t-1) | ... | tile n-1: S(n-2), S(n-1)   (D = 4 DMAs, S = 16 stores).  Tile t+1 is
     // published in tile t AHEAD of that tile's own operations (tile 0: behind them): what is younger than D(t+1) then gives
@@ -592,12 +511,10 @@ __global__ __launch_bounds__(512, 1) void apply_split_kernel(SplitApplyArgs a)
             else if (dma) tile_body(t, P0{}, T_{}, F_{}, F_{}, F_{});
             else tile_body(t, P0{}, F_{}, F_{}, F_{}, F_{});
         }
-#if !WC_SPLIT_DEFER
         // D0, table, D1, D2 | tile 0: D3, S0 | tile 1: D4, S1 | ... : 8, 20, 36 ... 36, 32
         // (with slots the table is complete before tile 0 and tile 1 is published EARLY in tile 0's loop, ahead of D3: younger than D1 is D2 only)
         else if (t == 0) {
-            if (PRE3) tile_body(t, P8{}, F_{}, T_{}, F_{}, F_{});          // (D3 went out in the prologue: younger than D1 are D2 and D3, as before)
-            else if (ASYNC_TABLE && !(WC_SPLIT_ABL & 8)) tile_body(t, P8{}, T_{}, T_{}, F_{}, F_{});
+            if (ASYNC_TABLE) tile_body(t, P8{}, T_{}, T_{}, F_{}, F_{});
             else tile_body(t, P4{}, T_{}, F_{}, F_{}, F_{});
         }
         else if (t == 1) tile_body(t, P20{}, T_{}, F_{}, F_{}, F_{});
@@ -605,22 +522,6 @@ __global__ __launch_bounds__(512, 1) void apply_split_kernel(SplitApplyArgs a)
         else if (t + 2 < n) tile_body(t, P36{}, F_{}, F_{}, F_{}, F_{});
         else if (t + 1 < n) tile_body(t, P32{}, F_{}, F_{}, F_{}, F_{});
         else tile_body(t, N_{}, F_{}, F_{}, F_{}, F_{});
-#else
-        else if (t == 0) tile_body(t, P8{}, T_{}, T_{}, F_{}, T_{});
-        else if (t == 1) tile_body(t, P4{}, T_{}, F_{}, T_{}, T_{});
-        else if (t == 2) tile_body(t, P20{}, T_{}, F_{}, T_{}, T_{});
-        else if (dma) tile_body(t, P36{}, T_{}, F_{}, T_{}, T_{});
-        else if (t + 2 < n) tile_body(t, P36{}, F_{}, F_{}, T_{}, T_{});
-        else if (t + 1 < n) tile_body(t, P32{}, F_{}, F_{}, T_{}, T_{});
-        else tile_body(t, N_{}, F_{}, F_{}, T_{}, F_{});
-#endif
-    }
-    if (WC_SPLIT_STAMPS && a.dbg && lane == 0) {
-        unsigned long long* d = a.dbg + ((int64_t)blockIdx.x * 8 + wave) * 16;
-        d[0] = t_wait; d[1] = t_loop; d[2] = t_store; d[3] = __builtin_amdgcn_s_memtime() - k0_;
-        d[4] = rt_in; d[5] = rt_loop; d[6] = __builtin_amdgcn_s_memrealtime();      // 100 MHz, chip-wide
-#pragma unroll
-        for (int i = 0; i < 8; ++i) d[8 + i] = pro_[i];
     }
 
     // Exact redo of every tile that STRADDLES samples of different slots (HW not a multiple of the tile): the MFMA pass used
@@ -687,13 +588,8 @@ hipError_t launch_apply_split(const SplitApplyArgs& a0, hipStream_t st)
     nwg = (a.ntiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
 #define WC_LAUNCH_SPLIT(SLOT_, MASK_, PL_)                                                                              \
     do {                                                                                                                \
-        static bool attr_set = false;                                                                                   \
-        if (!attr_set) {                                                                                                \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(apply_split_kernel<C, SLOT_, MASK_, PL_>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                   \
-            if (e != hipSuccess) return e;                                                                              \
-            attr_set = true;                                                                                            \
-        }                                                                                                               \
+        hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(apply_split_kernel<C, SLOT_, MASK_, PL_>), lds);     \
+        if (e != hipSuccess) return e;                                                                                   \
         hipLaunchKernelGGL((apply_split_kernel<C, SLOT_, MASK_, PL_>), dim3(nwg), dim3(512), lds, st, a);               \
     } while (0)
     const bool mask = a.maskout != nullptr;
@@ -718,8 +614,6 @@ hipError_t launch_apply_split(const SplitApplyArgs& a0, hipStream_t st)
 
 }  // namespace
 
-static void* g_split_dbg = nullptr;
-extern "C" void wc_dev_split_dbg(void* p) { g_split_dbg = p; }      // WC_SPLIT_STAMPS builds: where the stamps go (development only)
 
 bool wc_split_apply_supported(int64_t N, int64_t HW, int C)
 {
@@ -776,7 +670,7 @@ hipError_t wc_launch_apply_split(const void* xs, const float* xs_scale, const fl
         if (!oscale) return hipErrorInvalidValue;
         a.phi = static_cast<_Float16*>(planes); a.plo = a.phi + N * HW * C; a.oscale = oscale;
     }
-    a.dbg = static_cast<unsigned long long*>(dbg ? dbg : (WC_SPLIT_STAMPS ? g_split_dbg : nullptr));
+    a.dbg = static_cast<unsigned long long*>(dbg);
     (void)Kc;
     switch (C) {
         case 128: return launch_apply_split<128>(a, st);

@@ -29,18 +29,6 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#ifndef SXT_STAMPS
-#define SXT_STAMPS 0
-#endif
-#ifndef SXT_DMA_FRONT
-#define SXT_DMA_FRONT 0     // 1: a stage's DMA pieces leave right behind its barrier (0: behind the block-steps' MFMAs)
-#endif
-#ifndef SXT_ALT
-#define SXT_ALT 0      // 1: every other MFMA chain runs on the negated A fragments and is subtracted at the flush -- the matrix pipe's accumulation bias cancels (wc_fast_xty.hip, XTY_ALT; measured and left off: DESIGN.md section 2)
-#endif
-#ifndef SXT_ABL
-#define SXT_ABL 0      // development ablation bits: 1 no VALU statistics, 2 no fragment reads / MFMAs, 4 no DMAs after the prologue
-#endif
 
 namespace {
 
@@ -67,7 +55,6 @@ struct SplitXtxArgs {
     double* P;                               // [nslab][C][C], block-upper triangle
     float* colsum;                           // [nslab][C]: sum of g / s
     double* dfix;                            // [nslab][C]: sum of (g / s)^2
-    unsigned long long* dbg;
 };
 
 template <int C>
@@ -215,8 +202,6 @@ __global__ __launch_bounds__(512, 1) void xtx_split_kernel(SplitXtxArgs a)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
 
-    unsigned long long t0_ = 0, t_wait = 0, t_valu = 0, t_mfma = 0;
-    if (SXT_STAMPS) t0_ = __builtin_amdgcn_s_memtime();
 #pragma unroll
     for (int s = 0; s < 3; ++s) if (s < nst) dma_stage(s);
 
@@ -226,12 +211,9 @@ __global__ __launch_bounds__(512, 1) void xtx_split_kernel(SplitXtxArgs a)
     // own one block where waves 0-3 own two: a stage is one barrier interval for all eight waves, and with every wave in the
     // same phase the vector ALU (two float64 instructions per accumulator element and flush) and the matrix pipe took
     // turns -- the first version ran 12 vector instructions per MFMA, as many as the converting kernel, at 59 us.
-    auto stage = [&](int s, auto NL_, auto ZERO_, auto FL_, auto MODE_, bool neg) __attribute__((always_inline)) {
+    auto stage = [&](int s, auto NL_, auto ZERO_, auto FL_, auto MODE_) __attribute__((always_inline)) {
         constexpr int NL = decltype(NL_)::value;
         constexpr bool ZERO = decltype(ZERO_)::value, FL = decltype(FL_)::value;
-        const unsigned sgn = (SXT_ALT && neg) ? 0x80008000u : 0u;       // (wave-uniform: the sign of this stage's chain)
-        unsigned long long c0_ = 0;
-        if (SXT_STAMPS) c0_ = __builtin_amdgcn_s_memtime();
         // my pieces of stage s have landed (younger: my pieces of stages s+1 and s+2, where those exist)
         if (s + 2 < nst) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * PPW) : "memory");
         else if (s + 1 < nst) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PPW) : "memory");
@@ -239,31 +221,21 @@ __global__ __launch_bounds__(512, 1) void xtx_split_kernel(SplitXtxArgs a)
         // every wave's pieces of stage s have landed, and every wave has finished with stage s-1 (its fragments were consumed by
         // MFMAs, its statistics reads by the VALU): buffer (s+3) % 4 = (s-1) % 4 is free
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        const bool dma_on = s + 3 < nst && !(SXT_ABL & 4);
-        if (dma_on && (SXT_DMA_FRONT || (SXT_ABL & 2))) dma_stage(s + 3);
-        unsigned long long c1_ = 0;
-        if (SXT_STAMPS) { c1_ = __builtin_amdgcn_s_memtime(); t_wait += c1_ - c0_; }
+        const bool dma_on = s + 3 < nst;
         const char* sb = smem + (s & (NBUF - 1)) * STAGE;
         // block-step u = (k-step u / NL, block u % NL): its four fragments (two transposing reads each) in set u & 1
         f16x8 F[2][4];                                 // [set][A hi, A lo, B hi, B lo]
         auto read_a = [&](int set, int ks, int b) __attribute__((always_inline)) {
             const char* pa = sb + ks * (NB * 1024) + fa_off[b];
             F[set][0] = tr_read8(pa); F[set][1] = tr_read8(pa + 2 * NB * 1024);
-            if (SXT_ALT && sgn) {       // (a scalar branch: positive chains skip the eight v_xor)
-                typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-                F[set][0] = __builtin_bit_cast(f16x8, __builtin_bit_cast(u32x4v, F[set][0]) ^ sgn);
-                F[set][1] = __builtin_bit_cast(f16x8, __builtin_bit_cast(u32x4v, F[set][1]) ^ sgn);
-            }
         };
         auto read_b = [&](int set, int ks, int b) __attribute__((always_inline)) {
             const char* pb = sb + ks * (NB * 1024) + fb_off[b];
             F[set][2] = tr_read8(pb); F[set][3] = tr_read8(pb + 2 * NB * 1024);
         };
-        if (!(SXT_ABL & 2)) { read_a(0, 0, 0); read_b(0, 0, 0); }      // the first block-step's reads fly under the statistics pass
-        if (decltype(MODE_)::value != 0 && !(SXT_ABL & 1)) valu_stats(sb, FL, MODE_);
-        unsigned long long c2_ = 0;
-        if (SXT_STAMPS) { c2_ = __builtin_amdgcn_s_memtime(); t_valu += c2_ - c1_; }
-        if (!(SXT_ABL & 2)) {
+        read_a(0, 0, 0); read_b(0, 0, 0);      // the first block-step's reads fly under the statistics pass
+        if (decltype(MODE_)::value != 0) valu_stats(sb, FL, MODE_);
+        {
             constexpr int NU = 2 * NL;
             const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -281,7 +253,7 @@ __global__ __launch_bounds__(512, 1) void xtx_split_kernel(SplitXtxArgs a)
                 // this wave's DMA pieces of stage s+3 behind the block-steps' MFMAs (issued together behind the barrier, all
                 // eight waves at once, they cost the stage ~400 cycles: MI355X_MICROARCH.md prices a piece at 60 cycles among
                 // MFMAs and 100-185 in a busy phase)
-                if (!SXT_DMA_FRONT && dma_on) {
+                if (dma_on) {
 #pragma unroll
                     for (int i = u * PPW / NU; i < (u + 1) * PPW / NU; ++i) dma_piece(s + 3, i);
                 }
@@ -289,13 +261,11 @@ __global__ __launch_bounds__(512, 1) void xtx_split_kernel(SplitXtxArgs a)
             }
         }
         if (FL) {
-            const double fsg = sgn ? -1.0 : 1.0;
 #pragma unroll
             for (int b = 0; b < NL; ++b)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) { if (SXT_ALT) acc64[b][r] = __builtin_fma((double)acc[b][r], fsg, acc64[b][r]); else acc64[b][r] += (double)acc[b][r]; }
+                for (int r = 0; r < 16; ++r) acc64[b][r] += (double)acc[b][r];
         }
-        if (SXT_STAMPS) t_mfma += __builtin_amdgcn_s_memtime() - c2_;
     };
     using T_ = std::true_type; using F_ = std::false_type;
     using N1 = std::integral_constant<int, 1>; using N2 = std::integral_constant<int, 2>;
@@ -303,8 +273,8 @@ __global__ __launch_bounds__(512, 1) void xtx_split_kernel(SplitXtxArgs a)
     if (wave >= 4) {        // one block; chains [odd stage, even stage]; stage 0 continues the zero-initialised accumulator
         auto loop_b = [&](auto MODE_) __attribute__((always_inline)) {
             for (int s = 0; s < nst; s += 2) {      // chain k = stages 2k - 1 (zero start) and 2k (flush): stage s ends chain s / 2
-                stage(s, N1{}, F_{}, T_{}, MODE_, ((s >> 1) & 1) != 0);
-                stage(s + 1, N1{}, T_{}, F_{}, MODE_, (((s >> 1) + 1) & 1) != 0);
+                stage(s, N1{}, F_{}, T_{}, MODE_);
+                stage(s + 1, N1{}, T_{}, F_{}, MODE_);
             }
         };
         const int mode = (want_csum ? 1 : 0) | (want_dfix ? 2 : 0);
@@ -312,28 +282,20 @@ __global__ __launch_bounds__(512, 1) void xtx_split_kernel(SplitXtxArgs a)
         else if (mode == 2) loop_b(std::integral_constant<int, 2>{});
         else if (mode == 1) loop_b(std::integral_constant<int, 1>{});
         else loop_b(M0{});
-        if (SXT_ALT && (nst & 2)) {                                         // the last (odd) stage's half chain: negated when nst = 2 (mod 4)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc64[0][r] -= (double)acc[0][r];
-        } else
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc64[0][r] += (double)acc[0][r];      // the last (odd) stage's half chain
 #pragma unroll
         for (int e = 0; e < 8; ++e) lsq[e] += (double)sq[e];                // ... and its squares
     } else if (nlive == 2) {
         for (int s = 0; s < nst; s += 2) {          // chain k = stages 2k, 2k + 1
-            stage(s, N2{}, T_{}, F_{}, M0{}, ((s >> 1) & 1) != 0);
-            stage(s + 1, N2{}, F_{}, T_{}, M0{}, ((s >> 1) & 1) != 0);
+            stage(s, N2{}, T_{}, F_{}, M0{});
+            stage(s + 1, N2{}, F_{}, T_{}, M0{});
         }
     } else {
         for (int s = 0; s < nst; s += 2) {
-            stage(s, N1{}, T_{}, F_{}, M0{}, ((s >> 1) & 1) != 0);
-            stage(s + 1, N1{}, F_{}, T_{}, M0{}, ((s >> 1) & 1) != 0);
+            stage(s, N1{}, T_{}, F_{}, M0{});
+            stage(s + 1, N1{}, F_{}, T_{}, M0{});
         }
-    }
-    if (SXT_STAMPS && a.dbg && lane == 0) {
-        unsigned long long* d = a.dbg + ((int64_t)blockIdx.x * 8 + wave) * 4;
-        d[0] = t_wait; d[1] = t_valu; d[2] = t_mfma; d[3] = __builtin_amdgcn_s_memtime() - t0_;
     }
 
     // partial blocks out, scales undone exactly (powers of two)
@@ -388,13 +350,8 @@ template <int C>
 hipError_t launch_xtx_split(const SplitXtxArgs& a, hipStream_t st)
 {
     constexpr size_t lds = (size_t)4 * (2 * 2 * (C / 32)) * 1024;       // four stages: 128 KiB (C = 256), 64 KiB (C = 128)
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(xtx_split_kernel<C>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(xtx_split_kernel<C>), lds);
+    if (e != hipSuccess) return e;
     const int slab_groups = (a.nslab + 7) / 8;
     hipLaunchKernelGGL((xtx_split_kernel<C>), dim3(slab_groups * a.ntypes * 8), dim3(512), lds, st, a);
     return hipGetLastError();
@@ -402,8 +359,6 @@ hipError_t launch_xtx_split(const SplitXtxArgs& a, hipStream_t st)
 
 }  // namespace
 
-static void* g_sxt_dbg = nullptr;
-extern "C" void wc_dev_split_xtx_dbg(void* p) { g_sxt_dbg = p; }      // SXT_STAMPS builds (development only)
 
 // Plan: slabs of whole 64-row flush periods, ~ one workgroup per CU (wc_fast_xty_plan's rule).  Returns nslab (0 = not eligible).
 int wc_split_xtx_plan(int64_t N, int64_t HW, int C, int per_sample, int* nsplit, int64_t* rows_per_slab, int* ntypes)
@@ -433,7 +388,6 @@ hipError_t wc_launch_split_xtx(const void* xs, const float* scale, int64_t N, in
     a.xs = static_cast<const _Float16*>(xs); a.plane = N * HW * C; a.scale = scale; a.N = N; a.HW = HW;
     a.per_sample = per_sample; a.nsplit = nsplit; a.rows_per_slab = rows_per_slab; a.nslab = nslab; a.ntypes = ntypes;
     a.P = P; a.colsum = colsum; a.dfix = dfix;
-    a.dbg = static_cast<unsigned long long*>(SXT_STAMPS ? g_sxt_dbg : nullptr);
     switch (C) {
         case 128: return launch_xtx_split<128>(a, st);
         case 256: return launch_xtx_split<256>(a, st);
