@@ -480,7 +480,9 @@ int wc_bwd_apply_f32(const float* gy, const float* x, const float* mu, const flo
  *   run.py:269; 0 = inference: u, v are used as they are);  sigma = u^T W v;  w_sn = W / sigma.
  * u (rows) and v (cols) are updated in place when iterations > 0.  One launch of up to 32 co-resident workgroups that
  * meet through the last 16 bytes of `ws`: a buffer of wc_spectral_norm_workspace_bytes() that belongs to this weight,
- * ZEROED ONCE by the caller before its first use (every launch leaves the meeting words zero) and used by one launch at
+ * ZEROED ONCE by the caller before its first use (a zeroing allocation, never an uninitialised one: the meeting words are counters every
+ * workgroup increments, and the per-workgroup maxima beyond the launch's own keep the caller's zeros; every launch leaves the meeting
+ * words zero) and used by one launch at
  * a time.  rows + cols floats must fit the LDS (WC_ERR_SHAPE otherwise). */
 size_t wc_spectral_norm_workspace_bytes(int rows, int cols);
 /* After a forward call the 32 floats at this byte offset of `ws` hold per-workgroup maxima of |w_sn| (unused entries keep
@@ -567,7 +569,8 @@ int wc_conv_split_colsum_f32(const float* x, int64_t n, int relu, void* hi, void
                              float* colsum_partials, int C, wc_stream_t stream);
 
 /* The same split in ONE launch, its scale taken from the call before at the same call site (ABI 7).  `hist`: WC_CONV_HIST_FLOATS floats
- * that belong to the call site (one convolution's input, or its output gradient), zero-filled once and kept across calls: two arrays of
+ * that belong to the call site (one convolution's input, or its output gradient), zero-filled once by the caller before the site's first call
+ * (a zeroing allocation, never an uninitialised one: word WC_CONV_HIST_REDO is only ever incremented) and kept across calls: two arrays of
  * 512 (maximum, tag) pairs.  A call reads both, takes the array whose tags are all equal with the larger tag -- what the previous call
  * left -- and the power of two that puts THAT maximum into [2^7, 2^8): room for a 255-fold growth before fp16 overflows, precision to
  * 2^-20 of the tensor's maximum down to a 4000-fold shrink (hi + lo carry 22 bits wherever the scaled maximum lies in [2^-5, 65504]);
