@@ -12,20 +12,8 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-import os
-
 from . import _state, ops
 
-# K1 + K2 through the one-call entry wc_whiten_f32 (one launch less; identical results).  WC_WHITEN=0: the two separate calls.
-USE_WHITEN = os.environ.get('WC_WHITEN', '1') != '0'
-# the ReLU'd backward without a masked copy of the gradient (K4 and K6 both apply the bit mask; WC_BWD_BITS=0: K4 writes the copy)
-USE_BWD_BITS = os.environ.get('WC_BWD_BITS', '1') != '0'
-# the backward of a site on pre-split planes reads x from the planes too (wc_bwd_reduce_xsplit_f32 / wc_bwd_apply_xsplit_f32); WC_BWD_XSPLIT=0:
-# from the fp32 sum the producer then writes beside the planes
-USE_BWD_XSPLIT = os.environ.get('WC_BWD_XSPLIT', '1') != '0'
-# the residual add accumulates the next site's covariance partials in its own pass (wc_resadd_stats_split_f32; WC_FUSED_STATS=0: the
-# site runs its K1 on the planes the add wrote, as in round 4)
-USE_FUSED_STATS = os.environ.get('WC_FUSED_STATS', '1') != '0'
 # Test hook (tests/test_producer_gpu.py): {'record': []} collects the one-bit ReLU masks the sites of a pass produce, {'replay': [...]} makes
 # the sites of the next pass SAVE those instead of their own -- two routes whose K3 outputs differ in the last bit then run their backward
 # on identical masks, and their gradients can be compared at rounding level instead of at the level of a few flipped ReLUs.
@@ -51,159 +39,150 @@ def _allreduce_(tensors, group):
         off += n
 
 
+def _whiten(x, st, training, eps, momentum, ddof, moving_mean, moving_cov, group=None, groups=1):
+    """K1 + K2 of a site -> (mu, L, W, chan_scale), the statistics of the contiguous fp32 x (N, ..., C) or, where the residual add in
+    front wrote pre-split planes, of the SplitTensor st (x is then its handle; the planes' own scales are the apply's input scales).
+    Updates the moving statistics in place when training."""
+    C = x.shape[-1]
+    M = x.numel() // C
+    mm = moving_mean.view(-1) if moving_mean is not None else None
+    pre = training and st is not None and st.moments is not None and st.moments[1] == groups   # the producer accumulated K1's partials
+    if training and group is None and st is None:
+        # per-replica statistics (the reference's behaviour): K1 and K2 as one call -- the moments never leave the workspace and the
+        # K1 tail / K2 head run as one launch (wc_whiten_f32)
+        out = ops.whiten(x.view(M, C), eps, momentum, ddof, mm, moving_cov, groups)
+    elif training and group is None:
+        out = (ops.whiten_presummed if pre else ops.whiten_split)(st, eps, momentum, ddof, mm, moving_cov, groups)
+    else:
+        s = xtx = None
+        if training:
+            # sync-WC: the additive moments of all replicas, ONE collective on the buffer K1 wrote them into (no pack / unpack
+            # launches); every replica holds the same number of rows (fixed per-GPU batch): no host sync for the count
+            s, xtx, buf = (ops.stats(x.view(M, C), flat=True) if st is None else
+                           (ops.stats_presummed if pre else ops.stats_split)(st, flat=True))
+            dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+            M *= dist.get_world_size(group)
+        out = ops.factor(s, xtx, M, C, eps, momentum, ddof, training, mm, moving_cov, x.device, want_scale=st is None)
+    if training:
+        _touched(moving_mean, moving_cov)
+    return out if st is None else out + (st.scale,)
+
+
+def _k3(x, st, mu, A, bias, slot, plan, folded, relu, want_mask, handoff=None):
+    """K3 of a site -> (y, mask | None), from the fp32 x or from the SplitTensor st (x is then its handle; folded: `bias` is already
+    beta + (center - mu) A, one launch).  want_mask: also the ReLU's one-bit gradient mask.  handoff: None, or the (gamma, beta) of the
+    coloring when the output leaves as the next convolution's fp16 planes -- their scale record is built from those (not from the
+    effective bias K3 adds), and y is then the NaN handle that carries the planes (`_wc_planes`: what conv.fast_conv_or_none looks for)."""
+    rec = None if handoff is None else ops.out_scale(handoff[0], handoff[1], x.shape[-1], x.device)
+    if st is not None:
+        out = ops.apply_split(st, mu, A, bias, slot, plan=plan, relu=relu, folded=folded, want_mask=want_mask, oscale=rec)
+    elif rec is not None:
+        out = ops.apply_planes(x, mu, A, bias, slot, plan, rec, relu=relu, want_mask=want_mask)
+    else:
+        out = ops.apply(x, mu, A, bias, slot, plan=plan, relu=relu, want_mask=want_mask)
+    if rec is None:
+        return out if want_mask else (out, None)
+    y = _nan_handle(x.shape, x.device)
+    y._wc_planes = (out[0][0], out[0][1], rec)          # (hi, lo, scale record)
+    return y, (out[2] if want_mask else None)
+
+
+def backward_reads_planes(shape, has_slot):
+    """Do K4 and K6 of a site whose input arrives as pre-split planes read x from those planes too (wc_bwd_*_xsplit_f32: the C = 256 and
+    128 fast paths)?  Elsewhere they read the fp32 sum the producer then writes beside the planes.  (The fast paths need N*HW % 32 == 0:
+    a ReLU'd site on them always keeps its mask as bits.)"""
+    return ops.bwd_xsplit_supported(tuple(shape), has_slot)
+
+
+def _bwd_reduce(x, xs, mu, gy, y, slot, Kc, relu, bits, share, flat):
+    """K4 -> (R, gsum, flat buffer | None, scales | None, the gy K6 reads, K6's bit mask | None).  y: what the forward saved for a ReLU'd
+    site, its one-bit mask (bits) or y itself; K4 applies the mask while it stages gy and hands the masked gradient on (no pass of its
+    own).  share: the statistics path runs -- K4 samples the fp16 scales of (x - mu) and gy and K6 reuses them (three launches instead of
+    six).  flat: R and gsum as views of one buffer (sync-WC's single all-reduce)."""
+    rm = y if relu and bits else None
+    if xs is not None:          # x lives in the producer's planes
+        if rm is not None and gy.shape[-1] != 256:      # the planes forms of K4 / K6 apply the bits themselves at C = 256 only: one masking pass in front
+            gy, rm = ops.relu_mask_bits(gy, rm), None
+        out = ops.bwd_reduce_xsplit(xs, mu, gy, slot, Kc, relu_mask=rm, flat=flat)
+        return out[0], out[1], out[2] if flat else None, out[-1], gy, rm
+    # with the bits and a K6 that masks for itself (C = 256 fast paths) K4 writes no masked copy of the gradient at all
+    bits_only = rm is not None and share and ops.bwd_bits_supported(x.shape, slot is not None)
+    out = ops.bwd_reduce(x, mu, gy, slot, Kc, flat=flat, want_scales=share, relu_y=y if relu and not bits else None, relu_mask=rm,
+                         write_masked=not bits_only)
+    if relu and not bits_only:
+        gy = out[-2] if share else out[-1]
+    return out[0], out[1], out[2] if flat else None, out[-1] if share else None, gy, rm if bits_only else None
+
+
 class WhitenColorFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, slot, moving_mean, moving_cov, training, eps, momentum, ddof, process_group, relu=False,
-                planes_box=None, st=None):
+                handoff=False, st=None):
         # x: (N, ..., C) float32 contiguous (NHWC); gamma (Kc,C,C)|None; beta (Kc,C)|None; slot int32 (N,)|None
-        # planes_box: a list -> the output leaves as the next convolution's fp16 planes (conv_handoff below); the box receives them
+        # handoff: the output leaves as the next convolution's fp16 planes (the K3 -> convolution hand-off below): y is a handle carrying them
         # st: x is a HANDLE whose data is this ops.SplitTensor (the residual add wrote the pre-split planes, split_handle below):
         #     K1 and K3 run on the planes (wc_whiten_split_f16x2, wc_apply_split_ex_f16x2), no conversion, no fp32 read
         C = x.shape[-1]
         M_local = x.numel() // C
         dev = x.device
-        M = M_local
-        mm = moving_mean.view(-1) if moving_mean is not None else None
         if st is None:
             x = x.contiguous()
-        if st is not None:
-            pre = training and st.moments is not None and st.moments[1] == 1     # the producer accumulated K1's partials in its own pass
-            if training and process_group is None:
-                mu, L, W = (ops.whiten_presummed if pre else ops.whiten_split)(st, eps, momentum, ddof, mm, moving_cov)
-            else:
-                if training:       # sync-WC: the additive moments of all replicas, one collective on K1's own buffer
-                    s, xtx, buf = (ops.stats_presummed if pre else ops.stats_split)(st, flat=True)
-                    dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=process_group)
-                    M = M_local * dist.get_world_size(process_group)
-                else:
-                    s = xtx = None
-                mu, L, W = ops.factor(s, xtx, M, C, eps, momentum, ddof, training, mm, moving_cov, dev)
-            chan_scale = st.scale          # the planes' own scales are the apply's input scales
-        elif training and process_group is None and USE_WHITEN:
-            # per-replica statistics (the reference's behaviour): K1 and K2 as one call -- the moments never leave the workspace
-            # and the K1 tail / K2 head run as one launch (wc_whiten_f32; identical results to the two calls below)
-            mu, L, W, chan_scale = ops.whiten(x.view(M_local, C), eps, momentum, ddof, mm, moving_cov)
-        else:
-            if training and process_group is not None:
-                # sync-WC: the additive moments of all replicas, ONE collective on the buffer K1 wrote them into (no pack /
-                # unpack launches); every replica holds the same number of rows (fixed per-GPU batch): no host sync for the count
-                s, xtx, buf = ops.stats(x.view(M_local, C), flat=True)
-                dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=process_group)
-                M = M_local * dist.get_world_size(process_group)
-            elif training:
-                s, xtx = ops.stats(x.view(M_local, C))
-            else:
-                s = xtx = None
-            mu, L, W, chan_scale = ops.factor(s, xtx, M, C, eps, momentum, ddof, training, mm, moving_cov, dev, want_scale=True)
-        if training:
-            _touched(moving_mean, moving_cov)
+        mu, L, W, chan_scale = _whiten(x, st, training, eps, momentum, ddof, moving_mean, moving_cov, process_group)
         g = gamma.contiguous() if gamma is not None else None
         b = beta.contiguous() if beta is not None else None
+        bias = b
         if st is not None:      # ... and, on planes, the additive term beta + (center - mu) A from the same launch as the tables
-            A, At, plan, be = ops.color_split(W, g, st, mu, b)
+            A, At, plan, bias = ops.color_split(W, g, st, mu, b)
         else:
             A, At, plan = ops.color(W, g, chan_scale)      # plan: the apply's fp16 tables, so K3 is one launch
         # relu: folded into K3's epilogue (row N2).  Its gradient mask is kept as ONE BIT per element (K3 writes it): the
         # backward neither re-reads y (K4: 134 MB at the headline site) nor keeps y alive for it
         bits = bool(relu) and M_local % 32 == 0
+        y, mask = _k3(x, st, mu, A, bias, slot, plan, True, relu, bits, (g, b) if handoff else None)
+        ctx.xsplit = None
+        xs_t = ()
         if st is not None:
-            if planes_box is not None:
-                rec = ops.out_scale(g, b, C, dev)
-                out = ops.apply_split(st, None, A, be, slot, plan=plan, relu=relu, folded=True, want_mask=bits, oscale=rec)
-                planes_box.append((out[0], out[1], out[2] if bits else None))
-                y, mask = _nan_handle(x.shape, dev), planes_box[0][2]
-            elif bits:
-                y, mask = ops.apply_split(st, None, A, be, slot, plan=plan, relu=True, folded=True, want_mask=True)
-            else:
-                y, mask = ops.apply_split(st, None, A, be, slot, plan=plan, relu=relu, folded=True), None
-            # the backward: K4 / K6 read x from the same planes where they can (wc_bwd_*_xsplit_f32: C = 256 and 128 fast paths); elsewhere
-            # from the fp32 sum the producer wrote beside the planes (st.x32), or -- no such copy -- from one made here
-            ctx.xsplit = None
-            if any(ctx.needs_input_grad[:3]):
-                if USE_BWD_XSPLIT and ops.bwd_xsplit_supported(x.shape, slot is not None) and (not relu or bits):
-                    ctx.xsplit = (st.shape,)
-                    ctx.xs_tensors = (st.planes, st.center, st.scale)
-                    x = torch.empty(0, device=dev)
-                else:
-                    x = st.x32 if st.x32 is not None else ops.unsplit(st)
-            else:
+            # the backward: K4 / K6 read x from the same planes where they can; elsewhere from the fp32 sum the producer wrote beside
+            # the planes (st.x32), or -- no such copy -- from one made here
+            if not any(ctx.needs_input_grad[:3]):
                 x = torch.empty(0, device=dev)
-        elif planes_box is not None:
-            y = _apply_planes(x, mu, A, b, slot, plan, g, relu, bits, planes_box)
-            mask = planes_box[0][2]
-        elif bits:
-            y, mask = ops.apply(x, mu, A, b, slot, plan=plan, relu=True, want_mask=True)
-        else:
-            y, mask = ops.apply(x, mu, A, b, slot, plan=plan, relu=relu), None
+            elif backward_reads_planes(x.shape, slot is not None):
+                ctx.xsplit = st.shape
+                xs_t = (st.planes, st.center, st.scale)
+                x = torch.empty(0, device=dev)
+            else:
+                x = st.x32 if st.x32 is not None else ops.unsplit(st)
         if MASK_TAP is not None and bits:
             mask = _tap_mask(mask)
-        xs_t = getattr(ctx, 'xs_tensors', None) or ()
-        ctx.xs_tensors = None
         ctx.save_for_backward(x, mu, L, W, A, At, g if g is not None else torch.empty(0, device=dev),
                               slot if slot is not None else torch.empty(0, dtype=torch.int32, device=dev),
                               mask if bits else (y if relu else torch.empty(0, device=dev)), *xs_t)
-        if st is None:
-            ctx.xsplit = None
         ctx.relu = bool(relu)
         ctx.mask_bits = bits
         ctx.has_gamma = g is not None
         ctx.has_beta = b is not None
         ctx.has_slot = slot is not None
         ctx.training = bool(training)
-        ctx.eps, ctx.ddof, ctx.M, ctx.group = eps, ddof, M, process_group
+        # the row count K2 used: every replica's under sync-WC
+        ctx.M = M_local * dist.get_world_size(process_group) if (training and process_group is not None) else M_local
+        ctx.eps, ctx.ddof, ctx.group = eps, ddof, process_group
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, mu, L, W, A, At, g, slot, y = ctx.saved_tensors[:9]
-        xs = None
-        if ctx.xsplit is not None:          # x lives in the producer's planes: K4 / K6 read those
-            pl, cen, sc = ctx.saved_tensors[9:12]
-            xs = ops.SplitTensor(pl, cen, sc, None, ctx.xsplit[0])
+        xs = None if ctx.xsplit is None else ops.SplitTensor(*ctx.saved_tensors[9:12], None, ctx.xsplit)     # x lives in the planes
         g = g if ctx.has_gamma else None
         slot = slot if ctx.has_slot else None
         gy = gy.contiguous()
         need_x, need_g, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        Kc = A.shape[0]
-        dgamma = dbeta = dx = S = gmean = None
+        dgamma = dbeta = dx = S = gmean = scales = k6_mask = None
         stats_path = ctx.training and need_x
         want_g = ctx.has_gamma and need_g
         want_b = ctx.has_beta and need_b
-        reduce_runs = want_g or want_b or stats_path
-        if ctx.relu and not reduce_runs:  # the fused activation's gradient: the mask in front of the unchanged backward
-            if ctx.mask_bits:
-                gy = ops.relu_mask_bits(gy, y)
-            else:
-                gy = torch.ops.aten.threshold_backward(gy, y, 0.0)      # gy where y > 0, else 0: ONE elementwise pass (where(y > 0, ...) took three launches)
-        scales = None          # K4 samples the fp16 scales of (x - mu) and gy; K6 reuses them (three launches instead of six)
-        k6_mask = None
-        if reduce_runs:
-            share = bool(stats_path)
-            # K4 applies the mask while it stages gy and hands the masked gradient on (no pass of its own)
-            ry = y if (ctx.relu and not ctx.mask_bits) else None
-            rm = y if (ctx.relu and ctx.mask_bits) else None          # (the saved tensor is the bit mask then)
-            # with the bits and a K6 that masks for itself (C = 256 fast paths) K4 writes no masked copy of the gradient at all
-            bits_only = rm is not None and share and need_x and USE_BWD_BITS and ops.bwd_bits_supported(x.shape, slot is not None)
-            if xs is not None:
-                if rm is not None and gy.shape[-1] != 256:      # the planes forms of K4 / K6 apply the bits themselves at C = 256 only: one masking pass in front
-                    gy, rm = ops.relu_mask_bits(gy, rm), None
-                out = ops.bwd_reduce_xsplit(xs, mu, gy, slot, Kc, relu_mask=rm, flat=ctx.group is not None)
-                R, gsum = out[0], out[1]
-                rbuf = out[2] if ctx.group is not None else None
-                scales, k6_mask = out[-1], rm
-            else:
-                if ctx.group is None:
-                    out = ops.bwd_reduce(x, mu, gy, slot, Kc, want_scales=share, relu_y=ry, relu_mask=rm, write_masked=not bits_only)
-                    R, gsum = out[0], out[1]
-                else:
-                    out = ops.bwd_reduce(x, mu, gy, slot, Kc, flat=True, want_scales=share, relu_y=ry, relu_mask=rm, write_masked=not bits_only)
-                    R, gsum, rbuf = out[0], out[1], out[2]
-                if share:
-                    scales = out[-1]
-                if bits_only:
-                    k6_mask = rm
-                elif ry is not None or rm is not None:
-                    gy = out[-2] if share else out[-1]
+        if want_g or want_b or stats_path:
+            R, gsum, rbuf, scales, gy, k6_mask = _bwd_reduce(x, xs, mu, gy, y, slot, A.shape[0], ctx.relu, ctx.mask_bits, stats_path,
+                                                             ctx.group is not None)
             if ctx.group is None:
                 dgamma, dbeta, S, gmean = ops.bwd_factor(R, gsum, W, L, g, A, ctx.M, ctx.eps, ctx.ddof, stats_path,
                                                          want_dgamma=want_g, want_dbeta=want_b)
@@ -217,14 +196,20 @@ class WhitenColorFunction(torch.autograd.Function):
                     dist.all_reduce(rbuf, op=dist.ReduceOp.SUM, group=ctx.group)
                     _, _, S, gmean = ops.bwd_factor(R, gsum, W, L, g, A, ctx.M, ctx.eps, ctx.ddof, True,
                                                     want_dgamma=False, want_dbeta=False)
+        elif ctx.relu:          # the fused activation's gradient: the mask in front of the unchanged backward
+            if ctx.mask_bits:
+                gy = ops.relu_mask_bits(gy, y)
+            else:
+                gy = torch.ops.aten.threshold_backward(gy, y, 0.0)      # gy where y > 0, else 0: ONE elementwise pass (where(y > 0, ...) took three launches)
         if need_x:
-            if xs is not None and S is not None and scales is not None:
+            if xs is not None and S is not None:
                 dx = ops.bwd_apply_xsplit(gy, xs, mu, At, S, gmean, slot, scales, relu_mask=k6_mask)
             else:
-                if xs is not None and k6_mask is not None:          # (evaluation-mode site with a gradient: no statistics path, dx = masked gy At)
-                    gy, k6_mask = ops.relu_mask_bits(gy, k6_mask), None
-                dx = ops.bwd_apply(gy, x if xs is None else None, mu if xs is None else None, At, S if xs is None else None,
-                                   gmean if xs is None else None, slot, scales=scales if xs is None else None, relu_mask=k6_mask)
+                if xs is not None:          # (evaluation-mode site with a gradient: no statistics path, dx = masked gy At)
+                    x = mu = scales = None
+                    if k6_mask is not None:
+                        gy, k6_mask = ops.relu_mask_bits(gy, k6_mask), None
+                dx = ops.bwd_apply(gy, x, mu, At, S, gmean, slot, scales=scales, relu_mask=k6_mask)
         return dx, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None
 
 
@@ -249,21 +234,6 @@ def conv_handoff_supported(shape, relu, Ktables=1):
     """May a site of this NHWC output shape hand its output to the next convolution as planes? (relu'd sites only: that is what
     every convolution behind a WC site reads, generator.py:144-151)"""
     return bool(relu) and Ktables <= 1024 and ops.apply_planes_supported(tuple(shape))
-
-
-def _apply_planes(x, mu, A, b, slot, plan, gamma, relu, want_mask, box, beta=False):
-    # beta: the coloring's own bias where `b` is an effective one (grouped batches: b also carries the groups' mean offsets)
-    rec = ops.out_scale(gamma, b if beta is False else beta, x.shape[-1], x.device)
-    out = ops.apply_planes(x, mu, A, b, slot, plan, rec, relu=relu, want_mask=want_mask)
-    box.append((out[0], out[1], out[2] if want_mask else None))
-    return _nan_handle(x.shape, x.device)
-
-
-def attach_planes(handle, box):
-    """handle._wc_planes = (hi, lo, scale record): what conv.fast_conv_or_none looks for on its input."""
-    both, rec, _ = box[0]
-    handle._wc_planes = (both[0], both[1], rec)
-    return handle
 
 
 def split_of(x):
@@ -305,7 +275,7 @@ class ResidualAddFunction(torch.autograd.Function):
         if box is None:
             return ops.resadd(h, s, up)
         want32 = bool(x32) and any(ctx.needs_input_grad[:2])
-        if stat_groups and USE_FUSED_STATS and ops.resadd_stats_supported(h.shape, up, stat_groups):
+        if stat_groups and ops.resadd_stats_supported(h.shape, up, stat_groups):
             st = ops.resadd_stats_split(h, s, up, stat_groups, want_x32=want32)      # ... and K1's partials from the same pass
         else:
             st = ops.resadd_split(h, s, up, want_x32=want32)
@@ -362,58 +332,29 @@ def whiten_color_grouped(x, groups, gamma=None, beta=None, slot=None, moving_mea
         raise ValueError("N must be a multiple of groups")
     st = split_of(x)                    # the residual add in front wrote pre-split planes: K1 / K3 read those
     x = x.detach() if st is not None else x.detach().contiguous()
-    M = x.numel() // C
-    Mg = M // groups
     dev = x.device
-    mm = moving_mean.view(-1) if moving_mean is not None else None
-    if st is not None:
-        # K1 + K2 (wc_whiten_split_f16x2) -- or, where the residual add accumulated K1's partials itself, the tail + K2 only
-        pre = st.moments is not None and st.moments[1] == groups
-        mu, L, W = (ops.whiten_presummed if pre else ops.whiten_split)(st, eps, momentum, ddof, mm, moving_cov, groups)
-        cs = st.scale
-    elif USE_WHITEN:
-        mu, L, W, cs = ops.whiten(x.view(M, C), eps, momentum, ddof, mm, moving_cov, groups)      # K1 + K2 (wc_whiten_f32)
-    else:
-        s, xtx = ops.stats(x.view(M, C), groups)
-        mu, L, W, cs = ops.factor(s, xtx, Mg, C, eps, momentum, ddof, True, mm, moving_cov, dev, want_scale=True, groups=groups)
-    _touched(moving_mean, moving_cov)
+    mu, L, W, cs = _whiten(x, st, True, eps, momentum, ddof, moving_mean, moving_cov, None, groups)
     g = gamma.detach().contiguous() if gamma is not None else None
     b = beta.detach().contiguous() if beta is not None else None
-    def finish(center, A, bias, slots, plan):
-        # (the predicted scale follows from the coloring tables as given: every group's whitened batch has unit covariance)
-        handoff = planes and conv_handoff_supported(x.shape, relu, 1 if g is None else g.shape[0])
-        if st is not None:
-            be = bias            # (already beta - (mu_g - st.center) A: group_bias_centered)
-            if handoff:
-                rec = ops.out_scale(g, b, C, dev)
-                both, rec = ops.apply_split(st, None, A, be, slots, plan=plan, relu=relu, folded=True, oscale=rec)
-                return attach_planes(_nan_handle(x.shape, dev), [(both, rec, None)])
-            return ops.apply_split(st, None, A, be, slots, plan=plan, relu=relu, folded=True)
-        if handoff:
-            box = []
-            return attach_planes(_apply_planes(x, center, A, bias, slots, plan, g, relu, False, box, beta=b), box)
-        return ops.apply(x, center, A, bias, slots, plan=plan, relu=relu)
-
-    def gbias(A, Kc, per_group):
-        # on planes the common centre is the planes' own: the biases are then the additive terms of the split apply directly
-        if st is not None:
-            return st.center, ops.group_bias_centered(mu.view(groups, C), A, b, st.center, groups, Kc, per_group=per_group)
-        return ops.group_bias(mu.view(groups, C), A, b, groups, Kc, per_group=per_group)
-
+    if per_sample and (g is None or g.shape[0] != N):
+        raise ValueError("per_sample needs one coloring table per sample")
+    Kc = N // groups if per_sample else (1 if g is None else g.shape[0])
+    A, At, plan = ops.color(W, g, cs, groups, per_group=per_sample)
+    # on planes the common centre is the planes' own: the biases are then the additive terms of the split apply directly
+    # (beta - (mu_g - st.center) A, folded)
+    if st is not None:
+        center, bias = st.center, ops.group_bias_centered(mu.view(groups, C), A, b, st.center, groups, Kc, per_group=per_sample)
+    else:
+        center, bias = ops.group_bias(mu.view(groups, C), A, b, groups, Kc, per_group=per_sample)
     if per_sample:
-        if g is None or g.shape[0] != N:
-            raise ValueError("per_sample needs one coloring table per sample")
-        Kc = N // groups
-        A, At, plan = ops.color(W, g, cs, groups, per_group=True)
-        center, bias = gbias(A, Kc, True)
-        return finish(center, A, bias, _group_slot_base(N, N, 1, dev), plan)
-    Kc = 1 if g is None else g.shape[0]
-    A, At, plan = ops.color(W, g, cs, groups)
-    center, bias = gbias(A, Kc, False)
-    full_slot = _group_slot_base(N, groups, Kc, dev)
-    if slot is not None:
-        full_slot = (full_slot + slot.view(-1)).to(torch.int32).contiguous()
-    return finish(center, A, bias, full_slot, plan)
+        full_slot = _group_slot_base(N, N, 1, dev)
+    else:
+        full_slot = _group_slot_base(N, groups, Kc, dev)
+        if slot is not None:
+            full_slot = (full_slot + slot.view(-1)).to(torch.int32).contiguous()
+    # (the predicted scale of a hand-off follows from the coloring tables as given: every group's whitened batch has unit covariance)
+    handoff = planes and conv_handoff_supported(x.shape, relu, 1 if g is None else g.shape[0])
+    return _k3(x, st, center, A, bias, full_slot, plan, True, relu, False, (g, b) if handoff else None)[0]
 
 
 def _touched(*tensors):
@@ -453,25 +394,16 @@ class EvalPlan:
 def whiten_color_eval_cached(x, cache, gamma=None, beta=None, slot=None, moving_mean=None, moving_cov=None, eps=1e-3,
                              gamma_key=None, relu=False, planes=False):
     """Inference forward (no autograd) through an EvalPlan: one K3 launch per call once the plan is warm."""
-    C = x.shape[-1]
-    mu, A, At, plan = cache.get(C, gamma, moving_mean, moving_cov, eps, x.device, gamma_key)
+    mu, A, At, plan = cache.get(x.shape[-1], gamma, moving_mean, moving_cov, eps, x.device, gamma_key)
     b = beta.detach().contiguous() if beta is not None else None
     st = split_of(x)
     handoff = planes and conv_handoff_supported(x.shape, relu, A.shape[0])
     g = gamma.detach().contiguous() if (gamma is not None and handoff) else None
-    if st is not None:
-        # on planes: the cached A, with the tables for THIS tensor's scales and the additive term beta + (center - mu) A built
-        # inside the call (three launches; the planes' scales come from a sample of the data, not from the cached statistics)
-        if handoff:
-            rec = ops.out_scale(g, b, C, x.device)
-            both, rec = ops.apply_split(st, mu, A, b, slot, relu=relu, oscale=rec)
-            return attach_planes(_nan_handle(x.shape, x.device), [(both, rec, None)])
-        return ops.apply_split(st, mu, A, b, slot, relu=relu)
-    x = x.detach().contiguous()
-    if handoff:
-        box = []
-        return attach_planes(_apply_planes(x, mu, A, b, slot, plan, g, relu, False, box), box)
-    return ops.apply(x, mu, A, b, slot, plan=plan, relu=relu)
+    if st is None:
+        x = x.detach().contiguous()
+    # on planes: the cached A, with the tables for THIS tensor's scales and the additive term beta + (center - mu) A built
+    # inside the call (three launches; the planes' scales come from a sample of the data, not from the cached statistics)
+    return _k3(x, st, mu, A, b, slot, plan if st is None else None, False, relu, False, (g, b) if handoff else None)[0]
 
 
 def whiten_color(x, gamma=None, beta=None, slot=None, moving_mean=None, moving_cov=None, training=True,
@@ -480,15 +412,9 @@ def whiten_color(x, gamma=None, beta=None, slot=None, moving_mean=None, moving_c
     C % 32 == 0 (see layers for padding).  planes=True (relu'd sites whose consumer is conv.fast_conv): where K3 can, the
     result is a HANDLE -- a NaN tensor of y's shape without memory that carries the autograd edge -- with the output itself
     attached as the convolution's fp16 planes (handle._wc_planes); else the plain tensor."""
-    Kt = 1 if gamma is None else gamma.shape[0]
-    st = split_of(x)
-    if planes and conv_handoff_supported(x.shape, relu, Kt):
-        box = []
-        h = WhitenColorFunction.apply(x, gamma, beta, slot, moving_mean, moving_cov, bool(training),
-                                      float(eps), float(momentum), int(ddof), process_group, True, box, st)
-        return attach_planes(h, box)
+    handoff = planes and conv_handoff_supported(x.shape, relu, 1 if gamma is None else gamma.shape[0])
     return WhitenColorFunction.apply(x, gamma, beta, slot, moving_mean, moving_cov, bool(training),
-                                     float(eps), float(momentum), int(ddof), process_group, bool(relu), None, st)
+                                     float(eps), float(momentum), int(ddof), process_group, bool(relu), bool(handoff), split_of(x))
 
 
 _ROUTE = {}

@@ -37,9 +37,6 @@ from . import functional as WF
 _TLS = threading.local()          # per host thread: two trainers on two threads do not see each other's setting
 
 
-USE_FACTOR_MIX = os.environ.get("WC_FACTOR_MIX", "1") != "0"      # 0: the soft-assignment tables as torch matmul + add + gather (rounds 1-3)
-
-
 def _stat_groups():
     return getattr(_TLS, 'groups', 1)
 
@@ -400,7 +397,7 @@ class WhiteningColoring(nn.Module):
         the batch uses straight from the dictionary (wc_factor_mix_f32) -- no (K, C, C) table of all classes, no broadcast add, no gather."""
         fact = [br for br in self.branches if isinstance(br, FactorizedConv11)]
         rest = [br for br in self.branches if not isinstance(br, FactorizedConv11)]
-        if not USE_FACTOR_MIX or len(fact) != 1 or fact[0].use_bias or not all(type(br) is Conv11 for br in rest) or not x.is_cuda or cls is None:
+        if len(fact) != 1 or fact[0].use_bias or not all(type(br) is Conv11 for br in rest) or not x.is_cuda or cls is None:
             return None
         for br in self.branches:
             br._ensure(x)
@@ -466,10 +463,9 @@ class WhiteningColoring(nn.Module):
         return _stat_groups()
 
     def backward_takes_split(self, shape):
-        """Will the backward of this site read x from the planes as well (functional.USE_BWD_XSPLIT: K4 / K6 on planes)?  Then the
+        """Will the backward of this site read x from the planes as well (functional.backward_reads_planes: K4 / K6 on planes)?  Then the
         producer need not write an fp32 copy of the sum beside them."""
-        has_slot = any(br.conditional for br in self.branches)
-        return WF.USE_BWD_XSPLIT and self.npart.training and WF.ops.bwd_xsplit_supported(tuple(shape), has_slot)
+        return self.npart.training and WF.backward_reads_planes(shape, any(br.conditional for br in self.branches))
 
     def forward(self, x, cls=None, relu=False, planes=False):
         if isinstance(x, (list, tuple)):

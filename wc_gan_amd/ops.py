@@ -40,8 +40,59 @@ def _need(t, dtype, name, ndim=None):
         raise ValueError(f"{name} must be {ndim}-D, got shape {tuple(t.shape)}")
 
 
+def _need_table(bias, slot):
+    # the per-table inputs every K3 form takes, both optional
+    if bias is not None:
+        _need(bias, torch.float32, "bias", 2)
+    if slot is not None:
+        _need(slot, torch.int32, "slot", 1)
+
+
 def _workspace(nbytes, device):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+
+
+def _nhwc(shape):
+    """(N, HW, C) of an (N, ..., C) shape."""
+    HW = 1
+    for d in shape[1:-1]:
+        HW *= d
+    return shape[0], HW, shape[-1]
+
+
+def _moments_out(C, groups, flat, dev):
+    """K1's outputs (sum (C,), xtx (C, C)) float64, (G, ...) for groups > 1, and buf: with flat (groups == 1) the two are views of ONE
+    buffer, what sync-WC all-reduces in a single call; else None."""
+    if flat and groups == 1:
+        buf = torch.empty(C + C * C, dtype=torch.float64, device=dev)
+        return buf[:C], buf[C:].view(C, C), buf
+    lead = (groups,) if groups > 1 else ()
+    return (torch.empty(*lead, C, dtype=torch.float64, device=dev), torch.empty(*lead, C, C, dtype=torch.float64, device=dev), None)
+
+
+def _factor_out(C, groups, moving_mean, moving_cov, dev, want_scale=False):
+    """K2's outputs (mu (C,) f32, chan_scale (C,) f32 | None, L, W (C, C) f64), (G, ...) for groups > 1, after checking the moving
+    statistics it updates in place."""
+    if moving_mean is not None:
+        _need(moving_mean, torch.float32, "moving_mean")
+        _need(moving_cov, torch.float32, "moving_cov", 2)
+    lead = (groups,) if groups > 1 else ()
+    mu = torch.empty(*lead, C, dtype=torch.float32, device=dev)
+    chan_scale = torch.empty(C, dtype=torch.float32, device=dev) if want_scale else None
+    return mu, chan_scale, torch.empty(*lead, C, C, dtype=torch.float64, device=dev), torch.empty(*lead, C, C, dtype=torch.float64, device=dev)
+
+
+def _reduce_out(Kc, C, flat, dev):
+    """K4's outputs (R (Kc, C, C), gsum (Kc, C)) float64 and buf: with flat the two are views of ONE buffer (sync-WC's single all-reduce);
+    else None."""
+    if flat:
+        buf = torch.empty(Kc * (C * C + C), dtype=torch.float64, device=dev)
+        return buf[:Kc * C * C].view(Kc, C, C), buf[Kc * C * C:].view(Kc, C), buf
+    return torch.empty(Kc, C, C, dtype=torch.float64, device=dev), torch.empty(Kc, C, dtype=torch.float64, device=dev), None
+
+
+def _with_buf(out, buf):
+    return out if buf is None else out + (buf,)
 
 
 # Measurement hook (bench.py, tests): while TRACE is a list every K3 entry point appends (entry point, kernel it launches, a closure
@@ -69,34 +120,20 @@ def stats(x2d, groups=1, flat=False):
     lib = _lib.load()
     _need(x2d, torch.float32, "x", 2)
     M, C = x2d.shape
-    lead = (groups,) if groups > 1 else ()
-    buf = None
-    if flat and groups == 1:
-        buf = torch.empty(C + C * C, dtype=torch.float64, device=x2d.device)
-        s, xtx = buf[:C], buf[C:].view(C, C)
-    else:
-        s = torch.empty(*lead, C, dtype=torch.float64, device=x2d.device)
-        xtx = torch.empty(*lead, C, C, dtype=torch.float64, device=x2d.device)
+    s, xtx, buf = _moments_out(C, groups, flat, x2d.device)
     nb = lib.wc_stats_workspace_bytes(M, C, groups)
     if nb == 0:
         _lib.check(-3 if M % groups == 0 else -2, "wc_stats_f32")
     ws = _workspace(nb, x2d.device)
     _lib.check(lib.wc_stats_f32(_ptr(x2d), M, C, groups, _ptr(s), _ptr(xtx), _ptr(ws), ws.numel(), _stream()), "wc_stats_f32")
-    return (s, xtx, buf) if buf is not None else (s, xtx)
+    return _with_buf((s, xtx), buf)
 
 
 def factor(s, xtx, M, C, eps, momentum, ddof, training, moving_mean, moving_cov, device, want_scale=False, groups=1):
     """K2: -> (mu (C,) f32, L (C,C) f64, W (C,C) f64); updates the moving statistics in place when training.
     With want_scale=True also returns chan_scale (C,) f32, the power-of-two 1/sigma the fp16 fast path uses."""
     lib = _lib.load()
-    lead = (groups,) if groups > 1 else ()
-    mu = torch.empty(*lead, C, dtype=torch.float32, device=device)
-    chan_scale = torch.empty(C, dtype=torch.float32, device=device) if want_scale else None
-    L = torch.empty(*lead, C, C, dtype=torch.float64, device=device)
-    W = torch.empty(*lead, C, C, dtype=torch.float64, device=device)
-    if moving_mean is not None:
-        _need(moving_mean, torch.float32, "moving_mean")
-        _need(moving_cov, torch.float32, "moving_cov", 2)
+    mu, chan_scale, L, W = _factor_out(C, groups, moving_mean, moving_cov, device, want_scale)
     ws = _workspace(lib.wc_factor_workspace_bytes(C, groups), device)
     _lib.check(lib.wc_factor_f64(_ptr(s), _ptr(xtx), int(M), C, groups, float(eps), float(momentum), int(ddof), int(bool(training)),
                                  _ptr(moving_mean), _ptr(moving_cov), _ptr(mu), _ptr(chan_scale), _ptr(L), _ptr(W),
@@ -116,14 +153,7 @@ def whiten(x2d, eps, momentum, ddof, moving_mean, moving_cov, groups=1):
     _need(x2d, torch.float32, "x", 2)
     M, C = x2d.shape
     dev = x2d.device
-    lead = (groups,) if groups > 1 else ()
-    mu = torch.empty(*lead, C, dtype=torch.float32, device=dev)
-    chan_scale = torch.empty(C, dtype=torch.float32, device=dev)
-    L = torch.empty(*lead, C, C, dtype=torch.float64, device=dev)
-    W = torch.empty(*lead, C, C, dtype=torch.float64, device=dev)
-    if moving_mean is not None:
-        _need(moving_mean, torch.float32, "moving_mean")
-        _need(moving_cov, torch.float32, "moving_cov", 2)
+    mu, chan_scale, L, W = _factor_out(C, groups, moving_mean, moving_cov, dev, True)
     nb = lib.wc_whiten_workspace_bytes(M, C, groups)
     if nb == 0:
         _lib.check(-3 if M % groups == 0 else -2, "wc_whiten_f32")
@@ -271,13 +301,9 @@ def apply(x, mu, A, bias, slot, out=None, fast=True, plan=None, relu=False, want
     wc_apply_mask_f32) for bwd_reduce(relu_mask=...)."""
     lib = _lib.load()
     _need(x, torch.float32, "x")
-    N, C = x.shape[0], x.shape[-1]
-    HW = x.numel() // (N * C)
+    N, HW, C = _nhwc(x.shape)
     Kc = A.shape[0]
-    if bias is not None:
-        _need(bias, torch.float32, "bias", 2)
-    if slot is not None:
-        _need(slot, torch.int32, "slot", 1)
+    _need_table(bias, slot)
     y = torch.empty_like(x) if out is None else out
     ws = _workspace(lib.wc_apply_workspace_bytes(N, HW, C, Kc), x.device) if (fast and plan is None) else None
     traced = fast and plan is not None
@@ -299,11 +325,7 @@ def apply(x, mu, A, bias, slot, out=None, fast=True, plan=None, relu=False, want
 
 def apply_planes_supported(shape):
     """Can K3 leave the output of a site of this NHWC shape as the next convolution's planes (apply_planes)?"""
-    N, C = shape[0], shape[-1]
-    HW = 1
-    for d in shape[1:-1]:
-        HW *= d
-    return bool(_lib.load().wc_apply_planes_supported(N, HW, C))
+    return bool(_lib.load().wc_apply_planes_supported(*_nhwc(shape)))
 
 
 def out_scale(gamma, beta, C, device):
@@ -327,13 +349,9 @@ def apply_planes(x, mu, A, bias, slot, plan, oscale, relu=True, want_mask=False,
     oscale) [, mask]; y ~= (hi + lo) / oscale[0].  oscale: the record out_scale() made."""
     lib = _lib.load()
     _need(x, torch.float32, "x")
-    N, C = x.shape[0], x.shape[-1]
-    HW = x.numel() // (N * C)
+    N, HW, C = _nhwc(x.shape)
     Kc = A.shape[0]
-    if bias is not None:
-        _need(bias, torch.float32, "bias", 2)
-    if slot is not None:
-        _need(slot, torch.int32, "slot", 1)
+    _need_table(bias, slot)
     planes = torch.empty((2,) + tuple(x.shape), dtype=torch.float16, device=x.device) if _planes_out is None else _planes_out
     mask = (torch.empty((N * HW) // 32, C, dtype=torch.int32, device=x.device) if _mask_out is None else _mask_out) if want_mask else None
     _call(lib.wc_apply_planes_f32, (_ptr(x), _ptr(mu), _ptr(A), _ptr(bias), _ptr(slot), N, HW, C, Kc, 1 if relu else 0,
@@ -403,12 +421,7 @@ def unsplit(xs):
 
 
 def apply_split_supported(shape):
-    lib = _lib.load()
-    N, C = shape[0], shape[-1]
-    HW = 1
-    for d in shape[1:-1]:
-        HW *= d
-    return bool(lib.wc_apply_split_supported(N, HW, C))
+    return bool(_lib.load().wc_apply_split_supported(*_nhwc(shape)))
 
 
 def stats_split_supported(M, C, groups=1):
@@ -420,21 +433,14 @@ def stats_split(xs, groups=1, flat=False):
     lib = _lib.load()
     M, C = xs.M, xs.C
     dev = xs.planes.device
-    lead = (groups,) if groups > 1 else ()
-    buf = None
-    if flat and groups == 1:
-        buf = torch.empty(C + C * C, dtype=torch.float64, device=dev)
-        s, xtx = buf[:C], buf[C:].view(C, C)
-    else:
-        s = torch.empty(*lead, C, dtype=torch.float64, device=dev)
-        xtx = torch.empty(*lead, C, C, dtype=torch.float64, device=dev)
+    s, xtx, buf = _moments_out(C, groups, flat, dev)
     nb = lib.wc_stats_split_workspace_bytes(M, C, groups)
     if nb == 0:
         _lib.check(-2, "wc_stats_split_f16x2")
     ws = _workspace(nb, dev)
     _lib.check(lib.wc_stats_split_f16x2(_ptr(xs.planes), _ptr(xs.center), _ptr(xs.scale), M, C, groups, _ptr(s), _ptr(xtx),
                                         _ptr(ws), ws.numel(), _stream()), "wc_stats_split_f16x2")
-    return (s, xtx, buf) if buf is not None else (s, xtx)
+    return _with_buf((s, xtx), buf)
 
 
 def split_bias(A, bias, xs, mu):
@@ -460,14 +466,10 @@ def apply_split(xs, mu, A, bias, slot, plan=None, relu=False, out=None, folded=F
     oscale (the record out_scale() made): the output leaves as the next convolution's fp16 planes instead of y (wc_apply_split_ex_f16x2;
     the protocol of apply_planes) -> (planes (2, *shape) float16, oscale[, mask])."""
     lib = _lib.load()
-    N, C = xs.shape[0], xs.shape[-1]
-    HW = xs.M // N
+    N, HW, C = _nhwc(xs.shape)
     Kc = A.shape[0]
     dev = xs.planes.device
-    if bias is not None:
-        _need(bias, torch.float32, "bias", 2)
-    if slot is not None:
-        _need(slot, torch.int32, "slot", 1)
+    _need_table(bias, slot)
     if ws is None:
         ws = _workspace(lib.wc_apply_split_workspace_bytes(C, Kc), dev)
     mask = None
@@ -496,18 +498,11 @@ def whiten_split(xs, eps, momentum, ddof, moving_mean, moving_cov, groups=1):
     factor(*stats_split(xs, groups), ...) returns them.  The apply's input scales are xs.scale (give them to color())."""
     lib = _lib.load()
     M, C = xs.M, xs.C
-    dev = xs.planes.device
-    lead = (groups,) if groups > 1 else ()
-    mu = torch.empty(*lead, C, dtype=torch.float32, device=dev)
-    L = torch.empty(*lead, C, C, dtype=torch.float64, device=dev)
-    W = torch.empty(*lead, C, C, dtype=torch.float64, device=dev)
-    if moving_mean is not None:
-        _need(moving_mean, torch.float32, "moving_mean")
-        _need(moving_cov, torch.float32, "moving_cov", 2)
+    mu, _, L, W = _factor_out(C, groups, moving_mean, moving_cov, xs.planes.device)
     nb = lib.wc_whiten_split_workspace_bytes(M, C, groups)
     if nb == 0:
         _lib.check(-2, "wc_whiten_split_f16x2")
-    ws = _workspace(nb, dev)
+    ws = _workspace(nb, xs.planes.device)
     _lib.check(lib.wc_whiten_split_f16x2(_ptr(xs.planes), _ptr(xs.center), _ptr(xs.scale), M, C, groups, float(eps), float(momentum),
                                          int(ddof), _ptr(moving_mean), _ptr(moving_cov), _ptr(mu), _ptr(L), _ptr(W), _ptr(ws), ws.numel(),
                                          _stream()), "wc_whiten_split_f16x2")
@@ -535,6 +530,16 @@ def _resadd_args(h, s, up):
     return N, H, W, C
 
 
+def _split_out(h, want_x32):
+    """The producer's outputs for a sum of h's shape: (planes (2, M, C) f16, center, scale (C,) f32, flag (SPLIT_FLAG_WORDS,) int32,
+    x32: an fp32 copy of the sum when want_x32, else None)."""
+    N, H, W, C = h.shape
+    dev = h.device
+    return (torch.empty(2, N * H * W, C, dtype=torch.float16, device=dev), torch.empty(C, dtype=torch.float32, device=dev),
+            torch.empty(C, dtype=torch.float32, device=dev), torch.empty(SPLIT_FLAG_WORDS, dtype=torch.int32, device=dev),
+            torch.empty_like(h) if want_x32 else None)
+
+
 def resadd(h, s, up=False):
     """h + (upsample2x of) s as an fp32 tensor: h (N, H, W, C), s (N, H >> up, W >> up, C) or None."""
     lib = _lib.load()
@@ -550,12 +555,7 @@ def resadd_split(h, s, up=False, want_x32=False):
     (a reader without a planes path)."""
     lib = _lib.load()
     N, H, W, C = _resadd_args(h, s, up)
-    dev = h.device
-    planes = torch.empty(2, N * H * W, C, dtype=torch.float16, device=dev)
-    center = torch.empty(C, dtype=torch.float32, device=dev)
-    scale = torch.empty(C, dtype=torch.float32, device=dev)
-    flag = torch.empty(SPLIT_FLAG_WORDS, dtype=torch.int32, device=dev)
-    x32 = torch.empty_like(h) if want_x32 else None
+    planes, center, scale, flag, x32 = _split_out(h, want_x32)
     _lib.check(lib.wc_resadd_split_f32(_ptr(h), _ptr(s), N, H, W, C, 1 if up else 0, _ptr(planes), _ptr(center), _ptr(scale), _ptr(flag),
                                        _ptr(x32), _stream()), "wc_resadd_split_f32")
     return SplitTensor(planes, center, scale, flag, h.shape, x32)
@@ -573,16 +573,11 @@ def resadd_stats_split(h, s, up=True, groups=1, want_x32=False):
     hand it to whiten_presummed (K1 tail + K2) or stats_presummed (the raw moments).  `groups`: the consuming site's statistic groups."""
     lib = _lib.load()
     N, H, W, C = _resadd_args(h, s, up)
-    dev = h.device
     nb = lib.wc_resadd_stats_workspace_bytes(N, H, W, C, groups)
     if nb == 0 or not lib.wc_resadd_stats_supported(N, H, W, C, 1 if up else 0, groups):
         _lib.check(-2, "wc_resadd_stats_split_f32")
-    planes = torch.empty(2, N * H * W, C, dtype=torch.float16, device=dev)
-    center = torch.empty(C, dtype=torch.float32, device=dev)
-    scale = torch.empty(C, dtype=torch.float32, device=dev)
-    flag = torch.empty(SPLIT_FLAG_WORDS, dtype=torch.int32, device=dev)
-    x32 = torch.empty_like(h) if want_x32 else None
-    ws = _workspace(nb, dev)
+    planes, center, scale, flag, x32 = _split_out(h, want_x32)
+    ws = _workspace(nb, h.device)
     _lib.check(lib.wc_resadd_stats_split_f32(_ptr(h), _ptr(s), N, H, W, C, 1 if up else 0, int(groups), _ptr(planes), _ptr(center), _ptr(scale),
                                              _ptr(flag), _ptr(x32), _ptr(ws), ws.numel(), _stream()), "wc_resadd_stats_split_f32")
     return SplitTensor(planes, center, scale, flag, h.shape, x32, moments=(ws, int(groups)))
@@ -596,14 +591,7 @@ def whiten_presummed(xs, eps, momentum, ddof, moving_mean, moving_cov, groups=1)
     if g != groups:
         raise ValueError(f"the producer accumulated its partials for {g} statistic groups, the site asks for {groups}")
     M, C = xs.M, xs.C
-    dev = xs.planes.device
-    lead = (groups,) if groups > 1 else ()
-    mu = torch.empty(*lead, C, dtype=torch.float32, device=dev)
-    L = torch.empty(*lead, C, C, dtype=torch.float64, device=dev)
-    W = torch.empty(*lead, C, C, dtype=torch.float64, device=dev)
-    if moving_mean is not None:
-        _need(moving_mean, torch.float32, "moving_mean")
-        _need(moving_cov, torch.float32, "moving_cov", 2)
+    mu, _, L, W = _factor_out(C, groups, moving_mean, moving_cov, xs.planes.device)
     _lib.check(lib.wc_whiten_presummed_f16x2(_ptr(xs.center), M, C, groups, float(eps), float(momentum), int(ddof), _ptr(moving_mean),
                                              _ptr(moving_cov), _ptr(mu), _ptr(L), _ptr(W), _ptr(ws), ws.numel(), _stream()),
                "wc_whiten_presummed_f16x2")
@@ -619,18 +607,10 @@ def stats_presummed(xs, groups=1, flat=False):
     if g != groups:
         raise ValueError(f"the producer accumulated its partials for {g} statistic groups, the site asks for {groups}")
     M, C = xs.M, xs.C
-    dev = xs.planes.device
-    lead = (groups,) if groups > 1 else ()
-    buf = None
-    if flat and groups == 1:
-        buf = torch.empty(C + C * C, dtype=torch.float64, device=dev)
-        sm, xtx = buf[:C], buf[C:].view(C, C)
-    else:
-        sm = torch.empty(*lead, C, dtype=torch.float64, device=dev)
-        xtx = torch.empty(*lead, C, C, dtype=torch.float64, device=dev)
+    sm, xtx, buf = _moments_out(C, groups, flat, xs.planes.device)
     _lib.check(lib.wc_stats_presummed_f16x2(_ptr(xs.center), M, C, groups, _ptr(sm), _ptr(xtx), _ptr(ws), ws.numel(), _stream()),
                "wc_stats_presummed_f16x2")
-    return (sm, xtx, buf) if buf is not None else (sm, xtx)
+    return _with_buf((sm, xtx), buf)
 
 
 def patch_sum(g):
@@ -673,11 +653,7 @@ def unfold_channel_scale(D, db, scale, center):
 def bwd_bits_supported(shape, has_slot):
     """Can the ReLU'd backward of a site of this NHWC shape run without a masked copy of the gradient (bwd_reduce(..., relu_mask=,
     write_masked=False) + bwd_apply(..., relu_mask=))?"""
-    N, C = shape[0], shape[-1]
-    HW = 1
-    for d in shape[1:-1]:
-        HW *= d
-    return bool(_lib.load().wc_bwd_bits_supported(N, HW, C, int(bool(has_slot))))
+    return bool(_lib.load().wc_bwd_bits_supported(*_nhwc(shape), int(bool(has_slot))))
 
 
 def bwd_reduce(x, mu, gy, slot, Kc, flat=False, want_scales=False, relu_y=None, relu_mask=None, write_masked=True):
@@ -688,15 +664,8 @@ def bwd_reduce(x, mu, gy, slot, Kc, flat=False, want_scales=False, relu_y=None, 
     lib = _lib.load()
     _need(x, torch.float32, "x")
     _need(gy, torch.float32, "gy")
-    N, C = x.shape[0], x.shape[-1]
-    HW = x.numel() // (N * C)
-    buf = None
-    if flat:
-        buf = torch.empty(Kc * (C * C + C), dtype=torch.float64, device=x.device)
-        R, gsum = buf[:Kc * C * C].view(Kc, C, C), buf[Kc * C * C:].view(Kc, C)
-    else:
-        R = torch.empty(Kc, C, C, dtype=torch.float64, device=x.device)
-        gsum = torch.empty(Kc, C, dtype=torch.float64, device=x.device)
+    N, HW, C = _nhwc(x.shape)
+    R, gsum, buf = _reduce_out(Kc, C, flat, x.device)
     ws = _workspace(lib.wc_bwd_reduce_workspace_bytes(N, HW, C, Kc, int(slot is not None)), x.device)
     scales = torch.empty(2 * C, dtype=torch.float32, device=x.device) if want_scales else None
     gm = None
@@ -707,22 +676,20 @@ def bwd_reduce(x, mu, gy, slot, Kc, flat=False, want_scales=False, relu_y=None, 
             scales = torch.empty(2 * C, dtype=torch.float32, device=x.device)
         _lib.check(lib.wc_bwd_reduce_bits_f32(_ptr(x), _ptr(mu), _ptr(gy), _ptr(relu_mask), _ptr(slot), N, HW, C, Kc, _ptr(R), _ptr(gsum),
                                               _ptr(scales), _ptr(ws), ws.numel(), _stream()), "wc_bwd_reduce_bits_f32")
-        out = (R, gsum, buf) if buf is not None else (R, gsum)
-        return out + (scales,)
+        return _with_buf((R, gsum), buf) + (scales,)
     if relu_mask is not None:         # the mask in apply(..., want_mask=True)'s one-bit form: same outputs as relu_y
         _need(relu_mask, torch.int32, "relu_mask", 2)
         gm = torch.empty_like(gy)
         _lib.check(lib.wc_bwd_reduce_mask_f32(_ptr(x), _ptr(mu), _ptr(gy), _ptr(relu_mask), _ptr(slot), N, HW, C, Kc, _ptr(R), _ptr(gsum),
                                               _ptr(gm), _ptr(scales), _ptr(ws), ws.numel(), _stream()), "wc_bwd_reduce_mask_f32")
-        out = (R, gsum, buf) if buf is not None else (R, gsum)
-        out = out + (gm,)
+        out = _with_buf((R, gsum), buf) + (gm,)
         return out + (scales,) if want_scales else out
     if relu_y is not None:
         _need(relu_y, torch.float32, "relu_y")
         gm = torch.empty_like(gy)
     _lib.check(lib.wc_bwd_reduce_relu_f32(_ptr(x), _ptr(mu), _ptr(gy), _ptr(relu_y), _ptr(slot), N, HW, C, Kc, _ptr(R), _ptr(gsum),
                                           _ptr(gm), _ptr(scales), _ptr(ws), ws.numel(), _stream()), "wc_bwd_reduce_relu_f32")
-    out = (R, gsum, buf) if buf is not None else (R, gsum)
+    out = _with_buf((R, gsum), buf)
     if gm is not None:
         out = out + (gm,)
     return out + (scales,) if want_scales else out
@@ -731,11 +698,7 @@ def bwd_reduce(x, mu, gy, slot, Kc, flat=False, want_scales=False, relu_y=None, 
 def bwd_xsplit_supported(shape, has_slot):
     """Can K4 and K6 of a site of this NHWC shape read x from pre-split planes (bwd_reduce_xsplit / bwd_apply_xsplit: C = 256, the fast
     reduction and the one-pass K6; C = 128: the plain reduction and K6 as planes pass + accumulating pass)?  Then no fp32 copy of x has to exist for the backward."""
-    N, C = shape[0], shape[-1]
-    HW = 1
-    for d in shape[1:-1]:
-        HW *= d
-    return bool(_lib.load().wc_bwd_xsplit_supported(N, HW, C, int(bool(has_slot))))
+    return bool(_lib.load().wc_bwd_xsplit_supported(*_nhwc(shape), int(bool(has_slot))))
 
 
 def bwd_reduce_xsplit(xs, mu, gy, slot, Kc, relu_mask=None, flat=False):
@@ -743,16 +706,9 @@ def bwd_reduce_xsplit(xs, mu, gy, slot, Kc, relu_mask=None, flat=False):
     while gy is staged (gy is then the gradient before the ReLU; bwd_apply_xsplit(relu_mask=) masks for itself)."""
     lib = _lib.load()
     _need(gy, torch.float32, "gy")
-    N, C = gy.shape[0], gy.shape[-1]
-    HW = gy.numel() // (N * C)
+    N, HW, C = _nhwc(gy.shape)
     dev = gy.device
-    buf = None
-    if flat:
-        buf = torch.empty(Kc * (C * C + C), dtype=torch.float64, device=dev)
-        R, gsum = buf[:Kc * C * C].view(Kc, C, C), buf[Kc * C * C:].view(Kc, C)
-    else:
-        R = torch.empty(Kc, C, C, dtype=torch.float64, device=dev)
-        gsum = torch.empty(Kc, C, dtype=torch.float64, device=dev)
+    R, gsum, buf = _reduce_out(Kc, C, flat, dev)
     if relu_mask is not None:
         _need(relu_mask, torch.int32, "relu_mask", 2)
     ws = _workspace(lib.wc_bwd_reduce_workspace_bytes(N, HW, C, Kc, int(slot is not None)), dev)
@@ -760,7 +716,7 @@ def bwd_reduce_xsplit(xs, mu, gy, slot, Kc, relu_mask=None, flat=False):
     _lib.check(lib.wc_bwd_reduce_xsplit_f32(_ptr(xs.planes), _ptr(xs.center), _ptr(xs.scale), _ptr(mu), _ptr(gy), _ptr(relu_mask), _ptr(slot),
                                             N, HW, C, Kc, _ptr(R), _ptr(gsum), _ptr(scales), _ptr(ws), ws.numel(), _stream()),
                "wc_bwd_reduce_xsplit_f32")
-    return (R, gsum, buf, scales) if buf is not None else (R, gsum, scales)
+    return _with_buf((R, gsum), buf) + (scales,)
 
 
 def bwd_apply_xsplit(gy, xs, mu, At, S, gmean, slot, scales, relu_mask=None):
@@ -768,8 +724,7 @@ def bwd_apply_xsplit(gy, xs, mu, At, S, gmean, slot, scales, relu_mask=None):
     bwd_reduce_xsplit of the same site."""
     lib = _lib.load()
     _need(gy, torch.float32, "gy")
-    N, C = gy.shape[0], gy.shape[-1]
-    HW = gy.numel() // (N * C)
+    N, HW, C = _nhwc(gy.shape)
     Kc = At.shape[0]
     dx = torch.empty_like(gy)
     ws = _workspace(lib.wc_bwd_apply_xsplit_workspace_bytes(C, Kc), gy.device)
@@ -813,8 +768,7 @@ def bwd_apply(gy, x, mu, At, S, gmean, slot, fast=True, scales=None, relu_mask=N
     this its one-bit mask -- applied while gy is converted (wc_bwd_apply_bits_f32; bwd_bits_supported shapes, scales required)."""
     lib = _lib.load()
     _need(gy, torch.float32, "gy")
-    N, C = gy.shape[0], gy.shape[-1]
-    HW = gy.numel() // (N * C)
+    N, HW, C = _nhwc(gy.shape)
     Kc = At.shape[0]
     dx = torch.empty_like(gy)
     ws = _workspace(lib.wc_bwd_apply_workspace_bytes(N, HW, C, Kc), gy.device) if fast else None
