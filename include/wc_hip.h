@@ -660,6 +660,58 @@ int wc_conv_wrw_bias_f16x3(const void* xhi, const void* xlo, const float* xscale
 /* Bandwidth yardstick used by bench.py: dst[i] = src[i] (float4 grid-stride copy), same stream rules. */
 int wc_stream_copy_f32(const float* src, float* dst, int64_t n, wc_stream_t stream);
 
+/* ==== norm 'b': batch standardisation + diagonal coloring =================================================================================
+ * The second norm of create_norm's alphabet (generator.py:19-22), not a further route of the WC stages above -- so the rule "no new
+ * extension enters without one leaving" does not apply to this block, WC_CORE_API keeps its list and WC_ABI_VERSION its value (the
+ * entries are additive).  The site is the diagonal case of a WC site: the same (M, C) view, additive float64 moments, (table, slot)
+ * coloring with VECTORS gamma / beta [Kc, C], the block's ReLU behind it:
+ *     mu = sum / M,  var = sqsum / M - mu^2 (biased),  w = 1 / sqrt(var + eps)
+ *     a[k] = gamma[k] w,  b[k] = beta[k] - a[k] mu,   y = fmaf(a[slot], x, b[slot]),   relu: y = !(y <= 0) ? y : 0
+ * No matrix pipe: every kernel is an HBM stream.  The backward recomputes the ReLU's decision from x, a, b with the forward's own fmaf
+ * (bit for bit), so neither y nor a mask is kept.  M < 2^31 rows. */
+
+/* Raw additive moments (what a sync-BN would all-reduce): sum[g,c] = sum_m x[m,c], sqsum[g,c] = sum_m x[m,c]^2 over the M / groups
+ * consecutive rows of group g, float64, fixed summation order.  The statistics half of BatchNormalization(center=False, scale=False),
+ * generator.py:22. */
+size_t wc_std_stats_workspace_bytes(int64_t M, int C, int groups);
+int    wc_std_stats_f32(const float* x, int64_t M, int C, int groups, double* sum /*[groups,C]*/, double* sqsum /*[groups,C]*/,
+                        void* ws, size_t ws_bytes, wc_stream_t stream);
+
+/* Moments (training != 0) or moving statistics (training == 0: sum / sqsum ignored, may be NULL) -> mu, w [groups,C]; the moving
+ * statistics' update moving <- momentum moving + (1 - momentum) batch (variance times M / (M - ddof): ddof 0 is Keras, 1 is torch), the
+ * groups one after the other; and the tables a, b [groups*Kc, C], row g*Kc + k (gamma NULL = 1, beta NULL = 0).  M = rows per group.
+ * 0 < eps < 1, 0 <= momentum <= 1, ddof 0 | 1 (the ranges wc_factor_f64 takes; WC_ERR_ARG otherwise); training needs M > ddof.
+ * The normalising half of generator.py:22 and the centre / scale layers of generator.py:28-40 (CenterScale, ConditionalCenterScale). */
+int    wc_std_factor_f64(const double* sum, const double* sqsum, int64_t M, int C, int groups, double eps, double momentum, int ddof,
+                         int training, float* moving_mean /*[C] in/out, nullable*/, float* moving_variance /*[C] in/out, nullable*/,
+                         const float* gamma /*[Kc,C], nullable*/, const float* beta /*[Kc,C], nullable*/, int Kc,
+                         float* mu /*[groups,C]*/, float* w /*[groups,C]*/, float* a /*[groups*Kc,C]*/, float* b /*[groups*Kc,C]*/,
+                         wc_stream_t stream);
+
+/* y = fmaf(a[slot], x, b[slot]), relu != 0: the block's Activation('relu') (generator.py:155) in the same pass.  Kt = rows of a / b
+ * (groups*Kc; slot values are clamped into it).  The apply half of generator.py:22 + 28-40. */
+int    wc_std_apply_f32(const float* x, const float* a, const float* b, const int32_t* slot /*[N], nullable*/, int64_t N, int64_t HW,
+                        int C, int Kt, int relu, float* y, wc_stream_t stream);
+
+/* Backward (the TF graph gradients of the above, run.py:93-94).  g' = gy where the forward's fmaf(a, x, b) > 0 (relu != 0), else gy:
+ *     gsum[k,c] = sum_{m in slot k} g'[m,c]      gxsum[k,c] = sum_{m in slot k} g'[m,c] x[m,c]        (float64, fixed order)
+ * A slab of the reduction never straddles two samples when Kc > 1. */
+size_t wc_std_bwd_reduce_workspace_bytes(int64_t N, int64_t HW, int C, int Kc);
+int    wc_std_bwd_reduce_f32(const float* x, const float* gy, const float* a, const float* b, const int32_t* slot, int64_t N, int64_t HW,
+                             int C, int Kc, int relu, double* gsum /*[Kc,C]*/, double* gxsum /*[Kc,C]*/,
+                             void* ws, size_t ws_bytes, wc_stream_t stream);
+
+/* dbeta[k] = gsum[k], dgamma[k] = w (gxsum[k] - mu gsum[k])  (both nullable), and with m1 = sum_k gamma[k] dbeta[k] / M,
+ * m2 = sum_k gamma[k] dgamma[k] / M:  q = -w^2 m2,  r = w (w mu m2 - m1)   (training == 0: q = r = 0, the statistics are constants).
+ * M = N*HW.  run.py:93-94. */
+int    wc_std_bwd_factor_f64(const double* gsum, const double* gxsum, const float* mu /*[C]*/, const float* w /*[C]*/,
+                             const float* gamma /*[Kc,C], nullable*/, int64_t M, int C, int Kc, int training,
+                             float* dgamma /*[Kc,C]*/, float* dbeta /*[Kc,C]*/, float* q /*[C]*/, float* r /*[C]*/, wc_stream_t stream);
+
+/* dx = a[slot] g' + q x + r, the ReLU's decision recomputed as in wc_std_bwd_reduce_f32.  run.py:93-94. */
+int    wc_std_bwd_apply_f32(const float* x, const float* gy, const float* a, const float* b, const float* q, const float* r,
+                            const int32_t* slot, int64_t N, int64_t HW, int C, int Kc, int relu, float* dx, wc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,8 +152,19 @@ SIGNATURES = {
     "wc_conv_workspace_bytes": (c_size_t, [c_void_p]),
     "wc_conv_f16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                               c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wc_std_stats_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "wc_std_stats_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wc_std_factor_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_double, c_double, c_int, c_int, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wc_std_apply_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "wc_std_bwd_reduce_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
+    "wc_std_bwd_reduce_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wc_std_bwd_factor_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wc_std_bwd_apply_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int,
+                                     c_int, c_void_p, c_void_p]),
 }
-
 
 
 class SnItem(ctypes.Structure):          # wc_sn_item

@@ -9,7 +9,8 @@ submodule is empty); everything in-tree is cited.
 
     dense_1/kernel:0                       (128, 4*4*C)   Dense, generator.py:127 (unnamed: Keras' automatic name; any dense_N loads); /bias:0
     embedding_1/embeddings:0               (K, C)         Embedding of concat_cls generators (generator.py:120-121, run.py:175)
-    <name>_npart/moving_mean:0, /moving_variance:0        BatchNormalization(center=False, scale=False) of norm == 'b' (generator.py:22)
+    <name>_npart/moving_mean:0, /moving_variance:0        BatchNormalization(center=False, scale=False) of norm == 'b' (generator.py:22);
+                                           (C,) each, the same keys from torch's route and from the fused one (layers.BatchStandardization)
     Generator.<i>.conv1|conv2/kernel:0     (3, 3, Cin, Cout)  Conv2D of resblock `Generator.<i>` (generator.py:145); /bias:0
     Generator.<i>.shortcut/kernel:0        (1, 1, Cin, Cout)
     Generator.Final/kernel:0               (3, 3, C, 3)   generator.py:154-155; /bias:0
@@ -25,7 +26,8 @@ submodule is empty); everything in-tree is cited.
 
 Two conventions that differ and are NOT converted (no shipped recipe uses either; stated so that nobody is surprised): Keras'
 BatchNormalization stores the BIASED batch variance in moving_variance, torch's running_var the unbiased one (n / (n - 1) apart while
-training resumes: norm == 'b' generators only); and a spectral concat_cls generator upstream wraps its Embedding in SNEmbeding with a
+training resumes: norm == 'b' generators only -- layers.BatchStandardization, the fused route, follows Keras by default (ddof=0) and
+torch with ddof=1; a file saved from either route loads into the other as it is); and a spectral concat_cls generator upstream wraps its Embedding in SNEmbeding with a
 `/u:0` weight, where this build's Generator keeps a plain nn.Embedding (the key is then `embedding_<n>`, not `sn_embeding_<n>`).
 
 Layout conversions (torch here <-> Keras in the file): Conv2D kernel (Cout, Cin, kh, kw) <-> (kh, kw, Cin, Cout); Dense kernel
@@ -40,7 +42,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .layers import _Coloring, DecorelationNormalization
+from .layers import _Coloring, BatchStandardization, DecorelationNormalization
 
 
 def _dense_name(index, spectral):
@@ -63,7 +65,7 @@ def _entries(module):
     n_dense = n_emb = 0
     for m in module.modules():
         name = getattr(m, 'layer_name', None)
-        if isinstance(m, (DecorelationNormalization, _Coloring)) and name is not None:
+        if isinstance(m, (DecorelationNormalization, BatchStandardization, _Coloring)) and name is not None:
             for wn, t in list(m.named_parameters(recurse=False)) + list(m.named_buffers(recurse=False)):
                 if not wn.startswith('_'):
                     yield (f"{name}/{wn}:0", t) + ident

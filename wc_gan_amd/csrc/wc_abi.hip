@@ -1263,4 +1263,114 @@ int wc_spectral_norm_bwd_batched_f32(const wc_sn_bwd_item* items, int count, int
     return WC_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// norm 'b': batch standardisation + diagonal coloring (wc_std.hip)
+namespace {
+inline bool std_bad_rows(int64_t N, int64_t HW) { return N <= 0 || HW <= 0 || HW > INT32_MAX || N > INT32_MAX / HW; }
+inline bool std_bad_args(double eps, double momentum, int ddof)
+{
+    return !(eps > 0.0) || eps >= 1.0 || momentum < 0.0 || momentum > 1.0 || ddof < 0 || ddof > 1;
+}
+inline size_t std_partial_bytes(int64_t nseg, int64_t HWs, int C)
+{
+    int64_t rps;
+    return slot_bytes((size_t)nseg * wc_std_plan(HWs, C, &rps) * 2 * C, 8);
+}
+}  // namespace
+
+size_t wc_std_stats_workspace_bytes(int64_t M, int C, int groups)
+{
+    if (groups <= 0 || std_bad_rows(1, M) || (M % groups) != 0 || bad_channels(C)) return 0;
+    return std_partial_bytes(groups, M / groups, C);
+}
+
+int wc_std_stats_f32(const float* x, int64_t M, int C, int groups, double* sum, double* sqsum, void* ws, size_t ws_bytes,
+                     wc_stream_t stream)
+{
+    if (!x || !sum || !sqsum || !ws) return WC_ERR_NULL;
+    if (groups <= 0 || std_bad_rows(1, M) || (M % groups) != 0) return WC_ERR_SHAPE;
+    if (bad_channels(C)) return WC_ERR_CHANNELS;
+    if (ws_bytes < wc_std_stats_workspace_bytes(M, C, groups)) return WC_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* P = static_cast<double*>(ws);
+    WC_TRY(wc_launch_std_reduce(0, x, nullptr, nullptr, nullptr, nullptr, groups, M / groups, C, 1, 0, P, st));
+    WC_TRY(wc_launch_std_combine(P, nullptr, 1, groups, M / groups, C, groups, sum, sqsum, st));
+    return WC_OK;
+}
+
+int wc_std_factor_f64(const double* sum, const double* sqsum, int64_t M, int C, int groups, double eps, double momentum, int ddof,
+                      int training, float* moving_mean, float* moving_variance, const float* gamma, const float* beta, int Kc,
+                      float* mu, float* w, float* a, float* b, wc_stream_t stream)
+{
+    if (!mu || !w || !a || !b) return WC_ERR_NULL;
+    if (training ? (!sum || !sqsum) : (!moving_mean || !moving_variance)) return WC_ERR_NULL;
+    if ((moving_mean == nullptr) != (moving_variance == nullptr)) return WC_ERR_NULL;
+    if (M <= 0 || groups <= 0 || Kc <= 0 || (training && M <= ddof) || (!training && groups != 1)) return WC_ERR_SHAPE;
+    if (bad_channels(C)) return WC_ERR_CHANNELS;
+    if (std_bad_args(eps, momentum, ddof)) return WC_ERR_ARG;
+    WC_TRY(wc_launch_std_factor(sum, sqsum, M, C, groups, eps, momentum, ddof, training != 0, moving_mean, moving_variance, gamma, beta,
+                                Kc, mu, w, a, b, static_cast<hipStream_t>(stream)));
+    return WC_OK;
+}
+
+int wc_std_apply_f32(const float* x, const float* a, const float* b, const int32_t* slot, int64_t N, int64_t HW, int C, int Kt, int relu,
+                     float* y, wc_stream_t stream)
+{
+    if (!x || !a || !b || !y) return WC_ERR_NULL;
+    if (std_bad_rows(N, HW) || Kt <= 0) return WC_ERR_SHAPE;
+    if (bad_channels(C)) return WC_ERR_CHANNELS;
+    if (relu != 0 && relu != 1) return WC_ERR_ARG;
+    WC_TRY(wc_launch_std_apply(0, x, nullptr, a, b, nullptr, nullptr, slot, N, HW, C, Kt, relu, y, static_cast<hipStream_t>(stream)));
+    return WC_OK;
+}
+
+size_t wc_std_bwd_reduce_workspace_bytes(int64_t N, int64_t HW, int C, int Kc)
+{
+    if (std_bad_rows(N, HW) || Kc <= 0 || bad_channels(C)) return 0;
+    const size_t whole = std_partial_bytes(1, N * HW, C), per_sample = std_partial_bytes(N, HW, C);
+    return whole > per_sample ? whole : per_sample;
+}
+
+int wc_std_bwd_reduce_f32(const float* x, const float* gy, const float* a, const float* b, const int32_t* slot, int64_t N, int64_t HW,
+                          int C, int Kc, int relu, double* gsum, double* gxsum, void* ws, size_t ws_bytes, wc_stream_t stream)
+{
+    if (!x || !gy || !gsum || !gxsum || !ws) return WC_ERR_NULL;
+    if (relu && (!a || !b)) return WC_ERR_NULL;
+    if (std_bad_rows(N, HW) || Kc <= 0) return WC_ERR_SHAPE;
+    if (bad_channels(C)) return WC_ERR_CHANNELS;
+    if (relu != 0 && relu != 1) return WC_ERR_ARG;
+    if (ws_bytes < wc_std_bwd_reduce_workspace_bytes(N, HW, C, Kc)) return WC_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* P = static_cast<double*>(ws);
+    // one table row for everything (Kc == 1, or no slot): slabs tile all rows; else a slab stays inside its sample
+    const bool per_sample = Kc > 1 && slot != nullptr;
+    const int64_t nseg = per_sample ? N : 1, HWs = per_sample ? HW : N * HW;
+    const int32_t* sl = per_sample ? slot : nullptr;
+    WC_TRY(wc_launch_std_reduce(1, x, gy, a, b, sl, nseg, HWs, C, Kc, relu, P, st));
+    WC_TRY(wc_launch_std_combine(P, sl, 0, nseg, HWs, C, Kc, gsum, gxsum, st));
+    return WC_OK;
+}
+
+int wc_std_bwd_factor_f64(const double* gsum, const double* gxsum, const float* mu, const float* w, const float* gamma, int64_t M, int C,
+                          int Kc, int training, float* dgamma, float* dbeta, float* q, float* r, wc_stream_t stream)
+{
+    if (!gsum || !gxsum || !mu || !w || !q || !r) return WC_ERR_NULL;
+    if (M <= 0 || Kc <= 0) return WC_ERR_SHAPE;
+    if (bad_channels(C)) return WC_ERR_CHANNELS;
+    WC_TRY(wc_launch_std_bwd_factor(gsum, gxsum, mu, w, gamma, M, C, Kc, training != 0, dgamma, dbeta, q, r,
+                                    static_cast<hipStream_t>(stream)));
+    return WC_OK;
+}
+
+int wc_std_bwd_apply_f32(const float* x, const float* gy, const float* a, const float* b, const float* q, const float* r,
+                         const int32_t* slot, int64_t N, int64_t HW, int C, int Kc, int relu, float* dx, wc_stream_t stream)
+{
+    if (!x || !gy || !a || !b || !q || !r || !dx) return WC_ERR_NULL;
+    if (std_bad_rows(N, HW) || Kc <= 0) return WC_ERR_SHAPE;
+    if (bad_channels(C)) return WC_ERR_CHANNELS;
+    if (relu != 0 && relu != 1) return WC_ERR_ARG;
+    WC_TRY(wc_launch_std_apply(1, x, gy, a, b, q, r, Kc > 1 ? slot : nullptr, N, HW, C, Kc, relu, dx, static_cast<hipStream_t>(stream)));
+    return WC_OK;
+}
+
 }  // extern "C"

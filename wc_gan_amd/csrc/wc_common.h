@@ -244,6 +244,23 @@ int wc_split_xtx_plan(int64_t N, int64_t HW, int C, int per_sample, int* nsplit,
 hipError_t wc_launch_split_xtx(const void* xs, const float* scale, int64_t N, int64_t HW, int C, int per_sample, int nsplit,
                                int64_t rows_per_slab, int nslab, int ntypes, double* P, float* colsum, double* dfix, hipStream_t st);
 
+// ----- batch standardisation + diagonal coloring, norm 'b' (wc_std.hip) ----------------------
+int wc_std_plan(int64_t HWs, int C, int64_t* rows_per_slab);       // slabs of a segment of HWs rows: a function of (HWs, C) alone
+// mode 0: P[slab] = (sum x, sum x^2); mode 1: (sum g', sum g' x), g' = gy masked by the recomputed forward (relu); nseg segments of HWs rows
+hipError_t wc_launch_std_reduce(int mode, const float* x, const float* gy, const float* a, const float* b, const int32_t* slot,
+                                int64_t nseg, int64_t HWs, int C, int Kt, int relu, double* P, hipStream_t st);
+// fixed-order sum of the slabs: by_segment -> out[segment], else out[slot[segment]] (slot NULL: out[0]); Kout rows
+hipError_t wc_launch_std_combine(const double* P, const int32_t* slot, int by_segment, int64_t nseg, int64_t HWs, int C, int Kout,
+                                 double* out0, double* out1, hipStream_t st);
+hipError_t wc_launch_std_factor(const double* sum, const double* sqsum, int64_t M, int C, int groups, double eps, double momentum,
+                                int ddof, int training, float* moving_mean, float* moving_var, const float* gamma, const float* beta,
+                                int Kc, float* mu, float* w, float* a, float* b, hipStream_t st);
+hipError_t wc_launch_std_bwd_factor(const double* gsum, const double* gxsum, const float* mu, const float* w, const float* gamma,
+                                    int64_t M, int C, int Kc, int training, float* dgamma, float* dbeta, float* q, float* r,
+                                    hipStream_t st);
+hipError_t wc_launch_std_apply(int bwd, const float* x, const float* gy, const float* a, const float* b, const float* q, const float* r,
+                               const int32_t* slot, int64_t N, int64_t HW, int C, int Kt, int relu, float* out, hipStream_t st);
+
 // ----- small-matrix stage (wc_small.hip) -----------------------------------------------------
 
 // K1 tail: shifted fp32 partials -> raw float64 moments

@@ -17,6 +17,8 @@ from . import _state, ops
 # Test hook (tests/test_producer_gpu.py): {'record': []} collects the one-bit ReLU masks the sites of a pass produce, {'replay': [...]} makes
 # the sites of the next pass SAVE those instead of their own -- two routes whose K3 outputs differ in the last bit then run their backward
 # on identical masks, and their gradients can be compared at rounding level instead of at the level of a few flipped ReLUs.
+# The batch-norm sites use the same hook (generator._norm_relu): the fused route records `y > 0`, torch's route replays it as its ReLU
+# (tests/test_std_gpu.py).
 MASK_TAP = None
 
 
@@ -554,3 +556,82 @@ def whiten_color_modular(x, gamma=None, beta=None, slot=None, moving_mean=None, 
     else:
         A = torch.matmul(W.t().unsqueeze(0), gamma.to(torch.float64))
     return AffineRowsFunction.apply(x, mu64.to(torch.float32), A.to(torch.float32), beta, slot)
+
+
+# ---------------------------------------------------------------------------------------------
+# norm 'b': batch standardisation + diagonal coloring (csrc/wc_std.hip).  gamma / beta are (Kc, C) VECTORS: no C x C table exists here.
+# ---------------------------------------------------------------------------------------------
+def _std_tables(x, gamma, beta, moving_mean, moving_variance, training, eps, momentum, ddof, groups=1):
+    """moments -> factor of one site: (mu, w, a, b).  Evaluation mode reads the moving statistics (no pass over x)."""
+    C = x.shape[-1]
+    M = x.numel() // C
+    s = sq = None
+    if training:
+        s, sq = ops.std_stats(x.view(M, C), groups)
+    mu, w, a, b = ops.std_factor(s, sq, M // groups, C, eps, momentum, ddof, training, moving_mean, moving_variance, gamma, beta,
+                                 x.device, groups)
+    if training:
+        _touched(moving_mean, moving_variance)
+    return mu, w, a, b
+
+
+class StandardizeColorFunction(torch.autograd.Function):
+    """y = relu?(gamma[slot] (x - mu) / sqrt(var + eps) + beta[slot]) as moments -> factor -> apply; the backward is the closed form
+    (reduce -> factor -> apply) with the ReLU's decision recomputed from x and the forward's tables: nothing but x, the tables and the
+    (C,) statistics is kept."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, slot, moving_mean, moving_variance, training, eps, momentum, ddof, relu):
+        x = x.detach().contiguous()
+        g = gamma.detach().contiguous() if gamma is not None else None
+        b_ = beta.detach().contiguous() if beta is not None else None
+        mu, w, a, b = _std_tables(x, g, b_, moving_mean, moving_variance, training, eps, momentum, ddof)
+        y = ops.std_apply(x, a, b, slot, relu)
+        ctx.save_for_backward(x, g, slot, mu, w, a, b)
+        ctx.training, ctx.relu = training, relu
+        ctx.has_beta = beta is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, g, slot, mu, w, a, b = ctx.saved_tensors
+        gy = gy.contiguous()
+        Kc = a.shape[0]
+        C = x.shape[-1]
+        gsum, gxsum = ops.std_bwd_reduce(x, gy, a, b, slot, Kc, ctx.relu)
+        dgamma, dbeta, q, r = ops.std_bwd_factor(gsum, gxsum, mu.view(-1), w.view(-1), g, x.numel() // C, ctx.training,
+                                                 want_dgamma=g is not None and ctx.needs_input_grad[1],
+                                                 want_dbeta=ctx.has_beta and ctx.needs_input_grad[2])
+        dx = ops.std_bwd_apply(x, gy, a, b, q, r, slot, ctx.relu) if ctx.needs_input_grad[0] else None
+        return dx, dgamma, dbeta, None, None, None, None, None, None, None, None
+
+
+def standardize_color(x, gamma=None, beta=None, slot=None, moving_mean=None, moving_variance=None, training=True,
+                      eps=1e-3, momentum=0.99, ddof=0, relu=False):
+    """Batch standardisation fused with a diagonal coloring and, with relu=True, the ReLU behind it.  x (N, ..., C) float32 on the GPU,
+    C % 32 == 0; gamma, beta (Kc, C) or None (1 / 0); slot (N,) int32 picks a sample's row (None: row 0).  Training mode normalises
+    with the batch's biased variance and updates the moving statistics in place (variance times M / (M - ddof): 0 Keras, 1 torch);
+    evaluation mode normalises with the moving statistics: one apply launch behind one small table launch."""
+    return StandardizeColorFunction.apply(x, gamma, beta, slot, moving_mean, moving_variance, bool(training), float(eps),
+                                          float(momentum), int(ddof), bool(relu))
+
+
+def standardize_color_grouped(x, groups, gamma=None, beta=None, slot=None, moving_mean=None, moving_variance=None,
+                              eps=1e-3, momentum=0.99, ddof=0, relu=False):
+    """Training-mode forward of `groups` independent batches stacked along N (no autograd), as whiten_color_grouped: every run of
+    N / groups samples is standardised with its own statistics and the moving statistics take the groups' updates one after the other
+    -- bit for bit what `groups` separate calls give."""
+    N = x.shape[0]
+    if N % groups != 0:
+        raise ValueError("N must be a multiple of groups")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, gamma, beta)):
+        raise RuntimeError("standardize_color_grouped() is a forward-only path: wrap the call in torch.no_grad()")
+    x = x.detach().contiguous()
+    g = gamma.detach().contiguous() if gamma is not None else None
+    b_ = beta.detach().contiguous() if beta is not None else None
+    mu, w, a, b = _std_tables(x, g, b_, moving_mean, moving_variance, True, eps, momentum, ddof, groups)
+    Kc = a.shape[0] // groups
+    full_slot = _group_slot_base(N, groups, Kc, x.device)
+    if slot is not None and Kc > 1:
+        full_slot = (full_slot + slot.view(-1)).to(torch.int32).contiguous()
+    return ops.std_apply(x, a, b, full_slot, relu)

@@ -25,9 +25,10 @@ import torch.nn.functional as F
 import os
 
 from . import conv as fast_conv_mod
+from . import functional as WF
 from .functional import residual_add, split_of
-from .layers import (CenterScale, ConditionalCenterScale, ConditionalConv11, Conv11, DecorelationNormalization,
-                     FactorizedConv11, WhiteningColoring)
+from .layers import (BatchStandardization, CenterScale, ConditionalCenterScale, ConditionalConv11, Conv11,
+                     DecorelationNormalization, FactorizedConv11, StandardizeColoring, WhiteningColoring)
 
 # the block convolutions on the split-fp16 MFMA kernel where it takes the shape (WC_FAST_CONV=0: MIOpen everywhere)
 FAST_CONV = os.environ.get('WC_FAST_CONV', '1') != '0'
@@ -248,8 +249,10 @@ class _UnfusedStack(nn.Module):
 
 def create_norm(norm, after_norm, cls=None, number_of_classes=None, filters_emb=10,
                 uncoditional_conv_layer=Conv11, conditional_conv_layer=ConditionalConv11,
-                factor_conv_layer=FactorizedConv11, process_group=None):
-    """Factory of generator.py:13-90: returns result_norm(axis, name) -> stack(inp, cls)."""
+                factor_conv_layer=FactorizedConv11, process_group=None, fused_batch_norm=False):
+    """Factory of generator.py:13-90: returns result_norm(axis, name) -> stack(inp, cls).
+    fused_batch_norm: norm 'b' on the HIP route (layers.StandardizeColoring: GPU only, widths that are a multiple of 32) instead of
+    torch's BatchNorm2d followed by the coloring branches one by one; every other norm ignores it."""
     assert norm in NORMS
     assert after_norm in AFTER_NORMS
     K = number_of_classes
@@ -286,6 +289,8 @@ def create_norm(norm, after_norm, cls=None, number_of_classes=None, filters_emb=
             npart = DecorelationNormalization(name=name + '_npart', renorm=(norm == 'dr'), channels=channels,
                                               process_group=process_group)
             return WhiteningColoring(npart, br)
+        if norm == 'b' and fused_batch_norm:
+            return StandardizeColoring(BatchStandardization(name=name + '_npart', channels=channels), br)
         norm_layer = _BatchNormNoAffine(name=name + '_npart') if norm == 'b' else None
         return _UnfusedStack(norm_layer, br)
 
@@ -316,7 +321,19 @@ def _norm_relu(norm, x, cls, consumer=None, kind='same'):
     if isinstance(norm, WhiteningColoring):
         planes = consumer is not None and x.is_cuda and consumer.takes_planes(x.shape, kind)
         return norm(x, cls, relu=True, planes=planes)
-    return F.relu(norm(x, cls))
+    # functional.MASK_TAP is a test hook and None otherwise.  The batch-norm sites put BOOL tensors (y > 0) into the same 'record' list the WC sites
+    # fill with bit masks, and only torch's batch-norm route replays them: record and replay a generator whose ReLU'd sites are all of one kind
+    # (a list mixed from both kinds has no replayer).
+    if isinstance(norm, StandardizeColoring):
+        y = norm(x, cls, relu=True)             # fp32 out: this site has no planes form
+        if WF.MASK_TAP is not None and 'record' in WF.MASK_TAP:
+            WF.MASK_TAP['record'].append(y.detach() > 0)        # test hook (functional.MASK_TAP): this route's ReLU decisions ...
+        return y
+    out = norm(x, cls)
+    if (WF.MASK_TAP is not None and 'replay' in WF.MASK_TAP and isinstance(norm, _UnfusedStack)
+            and isinstance(norm.norm_layer, _BatchNormNoAffine)):
+        return out * WF.MASK_TAP['replay'].pop(0)               # ... taken over by torch's route: its gradients then differ by rounding only
+    return F.relu(out)
 
 
 class ResBlockUp(nn.Module):
@@ -453,14 +470,16 @@ def make_generator(input_noise_shape=(128,), output_channels=3, input_cls_shape=
                    block_norm='u', block_after_norm='cs', filters_emb=10,
                    last_norm='u', last_after_norm='cs', gan_type=None, arch='res',
                    spectral=False, fully_diff_spectral=False, spectral_iterations=1, conv_singular=True,
-                   process_group=None):
-    """Same keyword surface as generator.py:93-98; returns an nn.Module called as G(z) or G(z, cls)."""
+                   process_group=None, fused_batch_norm=False):
+    """Same keyword surface as generator.py:93-98; returns an nn.Module called as G(z) or G(z, cls).
+    fused_batch_norm: see create_norm."""
     assert arch in ['res', 'dcgan']
     if spectral and (block_after_norm not in ('uconv', 'ucs', 'n') or last_after_norm not in ('uconv', 'ucs', 'n')):
         raise NotImplementedError("spectral-normalised conditional coloring (SNConditionalConv11/SNFactorizedConv11) "
                                   "is outside the WC hot path; no shipped recipe sets --generator_spectral")
     conv_layer = partial(Conv2D, spectral=bool(spectral))
-    mk = partial(create_norm, number_of_classes=number_of_classes, filters_emb=filters_emb, process_group=process_group)
+    mk = partial(create_norm, number_of_classes=number_of_classes, filters_emb=filters_emb, process_group=process_group,
+                 fused_batch_norm=fused_batch_norm)
     block_norm_layer = mk(block_norm, block_after_norm)
     last_norm_layer = mk(last_norm, last_after_norm)
     return Generator(input_noise_shape, output_channels, first_block_shape, block_sizes, resamples,

@@ -68,7 +68,7 @@ class statistic_groups:
 def supports_statistic_groups(module):
     """True when every batch-statistics layer under `module` honours statistic_groups(): the fused Cholesky whitening at
     C % 32 == 0 without renorm.  ZCA, renorm ('dr'), zero-padded widths and plain batch norm ('b') do not -- callers run
-    separate passes instead (GanTrainer.generate)."""
+    separate passes instead (GanTrainer.generate).  The fused batch norm (BatchStandardization, C % 32 == 0) has the grouped form too."""
     for m in module.modules():
         if isinstance(m, DecorelationNormalization):
             if m.renorm or m.decomposition != 'cholesky' or (m.channels is not None and m.channels % 32 != 0):
@@ -77,6 +77,9 @@ def supports_statistic_groups(module):
                 return False                      # sync-WC: the grouped forward has no collective (per-replica statistics only)
             if m.channels is None:
                 return False                      # not built yet: width unknown
+        elif isinstance(m, BatchStandardization):
+            if m.channels is None or m.channels % 32 != 0:
+                return False                      # not built yet, or a width the HIP route does not take
         elif isinstance(m, (nn.BatchNorm1d, nn.BatchNorm2d)) or type(m).__name__ == '_BatchNormNoAffine':
             return False
     return True
@@ -478,3 +481,81 @@ class WhiteningColoring(nn.Module):
         # identity of the coloring weights (for the eval-mode plan cache); per-sample tables depend on cls -> no key
         key = None if per_sample else (_state.replays,) + tuple((p.data_ptr(), p._version) for p in self.parameters())
         return self.npart.transform(x, gamma, beta, slot, gamma_key=key, relu=relu, per_sample=per_sample, planes=planes)
+
+
+# ---------------------------------------------------------------------------------------------
+# norm 'b' on the HIP route (create_norm(..., fused_batch_norm=True))
+# ---------------------------------------------------------------------------------------------
+class BatchStandardization(_Lazy):
+    """BatchNormalization(center=False, scale=False) (generator.py:22) on NHWC.  State as Keras' layer keeps it: moving_mean (C,) zeros,
+    moving_variance (C,) ones.  ddof: what the moving variance is scaled by, M / (M - ddof) -- 0 is Keras (the reference), 1 is what
+    torch's running_var holds.  momentum and epsilon are [UPSTREAM-RECALL] (Keras' defaults are 0.99 / 1e-3)."""
+
+    def __init__(self, name=None, momentum=0.99, epsilon=1e-3, ddof=0, axis=-1, channels=None):
+        if axis not in (-1, 3):
+            raise ValueError("the HIP path is NHWC: axis must be -1")
+        self.momentum, self.epsilon, self.ddof = float(momentum), float(epsilon), int(ddof)
+        super().__init__(name, channels)
+
+    def build(self, C, device=None):
+        self.register_buffer('moving_mean', torch.zeros(C, device=device))
+        self.register_buffer('moving_variance', torch.ones(C, device=device))
+
+    def transform(self, x, gamma=None, beta=None, slot=None, relu=False):
+        """Standardisation fused with a diagonal coloring (gamma, beta (Kc, C), slot (N,)) and the ReLU behind it."""
+        self._ensure(x)
+        C = self.channels
+        if not x.is_cuda:
+            raise WF.ops._lib.WcHipError(f"{self.layer_name}: the fused batch norm runs on the GPU only (no CPU fallback); "
+                                         "create_norm(..., fused_batch_norm=False) keeps torch's")
+        if C % 32 != 0:
+            raise WF.ops._lib.WcHipError(f"{self.layer_name}: the fused batch norm takes widths that are a multiple of 32, got {C}")
+        groups = _stat_groups() if self.training else 1
+        if groups > 1:
+            return WF.standardize_color_grouped(x, groups, gamma, beta, slot, self.moving_mean, self.moving_variance,
+                                                self.epsilon, self.momentum, self.ddof, relu=relu)
+        return WF.standardize_color(x, gamma, beta, slot, self.moving_mean, self.moving_variance, self.training,
+                                    self.epsilon, self.momentum, self.ddof, relu=relu)
+
+    def forward(self, x):
+        return self.transform(x)
+
+
+class StandardizeColoring(nn.Module):
+    """`stack(inp)` of generator.py:83-87 for norm 'b'.  Branches that are all CenterScale / ConditionalCenterScale (after-norm ucs,
+    ccs, uccs) or none ('n'): their vectors add into one (gamma (Kc, C), beta (Kc, C), slot) and the site is moments -> factor ->
+    apply with the ReLU inside.  Any dense branch (uconv, cconv, fconv, ...): the standardisation runs as the same op without a
+    coloring, the branches run on its output one by one and are added, then the ReLU."""
+
+    def __init__(self, npart: BatchStandardization, branches):
+        super().__init__()
+        self.npart = npart
+        self.branches = nn.ModuleList(branches)
+
+    @property
+    def diagonal(self):
+        return all(type(br) in (CenterScale, ConditionalCenterScale) for br in self.branches)
+
+    def coloring_vectors(self, x, cls):
+        gamma = beta = slot = None
+        for br in self.branches:
+            br._ensure(x)
+            g, b = (br.gamma, br.beta) if br.conditional else (br.gamma.view(1, -1), br.beta.view(1, -1))
+            if br.conditional:
+                slot = _cls_index(cls)
+            gamma = g if gamma is None else gamma + g           # (1, C) broadcasts against (K, C)
+            beta = b if beta is None else beta + b
+        return gamma, beta, slot
+
+    def forward(self, x, cls=None, relu=False, planes=False):
+        if isinstance(x, (list, tuple)):
+            x, cls = x
+        if self.diagonal:
+            gamma, beta, slot = self.coloring_vectors(x, cls)
+            return self.npart.transform(x, gamma, beta, slot, relu=relu)
+        out = self.npart.transform(x)
+        total = None
+        for br in self.branches:
+            y = br([out, cls]) if br.conditional else br(out)
+            total = y if total is None else total + y
+        return F.relu(total) if relu else total

@@ -879,3 +879,140 @@ def spectral_norm_bwd_batched(gs, w_sns, us, vs, sigmas, wss, fully_diff):
     _lib.check(lib.wc_spectral_norm_bwd_batched_f32(ctypes.addressof(items), n, 1 if fully_diff else 0, _stream()),
                "wc_spectral_norm_bwd_batched_f32")
     return dWs
+
+
+# ---------------------------------------------------------------------------------------------
+# norm 'b': batch standardisation + diagonal coloring (csrc/wc_std.hip; include/wc_hip.h, the wc_std_* block)
+# ---------------------------------------------------------------------------------------------
+def _need_vec(t, name, C, rows=None):
+    _need(t, torch.float32, name, 2)
+    if t.shape[1] != C or (rows is not None and t.shape[0] != rows):
+        raise ValueError(f"{name} must be ({'Kc' if rows is None else rows}, {C}), got {tuple(t.shape)}")
+
+
+def std_stats(x2d, groups=1):
+    """x2d (M, C) float32 -> (sum, sqsum) (groups, C) float64: the raw additive moments of each run of M / groups rows."""
+    lib = _lib.load()
+    _need(x2d, torch.float32, "x", 2)
+    M, C = x2d.shape
+    nb = lib.wc_std_stats_workspace_bytes(M, C, groups)
+    if nb == 0:
+        _lib.check(-3 if (M > 0 and groups > 0 and M % groups == 0) else -2, "wc_std_stats_f32")
+    s = torch.empty(groups, C, dtype=torch.float64, device=x2d.device)
+    sq = torch.empty(groups, C, dtype=torch.float64, device=x2d.device)
+    ws = _workspace(nb, x2d.device)
+    _call(lib.wc_std_stats_f32, (_ptr(x2d), M, C, groups, _ptr(s), _ptr(sq), _ptr(ws), ws.numel()), "wc_std_stats_f32",
+          "wc_std_stats_f32", "std_reduce_kernel", (x2d, s, sq, ws))
+    return s, sq
+
+
+def std_factor(s, sq, M, C, eps, momentum, ddof, training, moving_mean, moving_variance, gamma, beta, device, groups=1):
+    """-> (mu, w (groups, C) f32, a, b (groups*Kc, C) f32); updates the moving statistics in place when training.  M: rows per group;
+    gamma / beta (Kc, C) float32 or None."""
+    lib = _lib.load()
+    for t, name in ((moving_mean, "moving_mean"), (moving_variance, "moving_variance")):
+        if t is not None:
+            _need(t, torch.float32, name, 1)
+    Kc = 1
+    for t, name in ((gamma, "gamma"), (beta, "beta")):
+        if t is not None:
+            _need_vec(t, name, C)
+            Kc = t.shape[0]
+    if gamma is not None and beta is not None and gamma.shape != beta.shape:
+        raise ValueError("gamma and beta must have the same shape")
+    mu = torch.empty(groups, C, dtype=torch.float32, device=device)
+    w = torch.empty(groups, C, dtype=torch.float32, device=device)
+    a = torch.empty(groups * Kc, C, dtype=torch.float32, device=device)
+    b = torch.empty(groups * Kc, C, dtype=torch.float32, device=device)
+    _call(lib.wc_std_factor_f64, (_ptr(s), _ptr(sq), int(M), C, groups, float(eps), float(momentum), int(ddof), int(bool(training)),
+                                  _ptr(moving_mean), _ptr(moving_variance), _ptr(gamma), _ptr(beta), Kc,
+                                  _ptr(mu), _ptr(w), _ptr(a), _ptr(b)), "wc_std_factor_f64")
+    return mu, w, a, b
+
+
+def std_apply(x, a, b, slot=None, relu=False):
+    """y = fmaf(a[slot], x, b[slot]) (relu: max(., 0), NaN kept).  x (N, ..., C) float32; a, b (Kt, C); slot (N,) int32 or None."""
+    lib = _lib.load()
+    _need(x, torch.float32, "x")
+    N, HW, C = _nhwc(x.shape)
+    _need_vec(a, "a", C)
+    _need_vec(b, "b", C, a.shape[0])
+    if slot is not None:
+        _need(slot, torch.int32, "slot", 1)
+        if slot.shape[0] != N:
+            raise ValueError("slot must hold one entry per sample")
+    y = torch.empty_like(x)
+    _call(lib.wc_std_apply_f32, (_ptr(x), _ptr(a), _ptr(b), _ptr(slot), N, HW, C, a.shape[0], int(bool(relu)), _ptr(y)),
+          "wc_std_apply_f32", "wc_std_apply_f32", "std_apply_kernel", (x, a, b, slot, y))
+    return y
+
+
+def std_bwd_reduce(x, gy, a, b, slot, Kc, relu=False):
+    """-> (gsum, gxsum) (Kc, C) float64 of g' = gy masked by the recomputed forward (relu) per coloring slot."""
+    lib = _lib.load()
+    _need(x, torch.float32, "x")
+    _need(gy, torch.float32, "gy")
+    if gy.shape != x.shape:
+        raise ValueError("gy must have x's shape")
+    N, HW, C = _nhwc(x.shape)
+    _need_vec(a, "a", C, Kc)
+    _need_vec(b, "b", C, Kc)
+    if slot is not None:
+        _need(slot, torch.int32, "slot", 1)
+    gsum = torch.empty(Kc, C, dtype=torch.float64, device=x.device)
+    gxsum = torch.empty(Kc, C, dtype=torch.float64, device=x.device)
+    nb = lib.wc_std_bwd_reduce_workspace_bytes(N, HW, C, Kc)
+    if nb == 0:
+        _lib.check(-3 if (N > 0 and HW > 0 and Kc > 0) else -2, "wc_std_bwd_reduce_f32")
+    ws = _workspace(nb, x.device)
+    _call(lib.wc_std_bwd_reduce_f32, (_ptr(x), _ptr(gy), _ptr(a), _ptr(b), _ptr(slot), N, HW, C, Kc, int(bool(relu)),
+                                      _ptr(gsum), _ptr(gxsum), _ptr(ws), ws.numel()),
+          "wc_std_bwd_reduce_f32", "wc_std_bwd_reduce_f32", "std_reduce_kernel", (x, gy, a, b, slot, gsum, gxsum, ws))
+    return gsum, gxsum
+
+
+def std_bwd_factor(gsum, gxsum, mu, w, gamma, M, training=True, want_dgamma=True, want_dbeta=True):
+    """-> (dgamma, dbeta (Kc, C) f32 | None, q, r (C,) f32): the coefficients of dx = a g' + q x + r."""
+    lib = _lib.load()
+    _need(gsum, torch.float64, "gsum", 2)
+    _need(gxsum, torch.float64, "gxsum", 2)
+    Kc, C = gsum.shape
+    _need(mu, torch.float32, "mu")
+    _need(w, torch.float32, "w")
+    if mu.numel() != C or w.numel() != C or gxsum.shape != gsum.shape:
+        raise ValueError("mu, w must hold C entries and gxsum must have gsum's shape")
+    if gamma is not None:
+        _need_vec(gamma, "gamma", C, Kc)
+    dev = gsum.device
+    dgamma = torch.empty(Kc, C, dtype=torch.float32, device=dev) if want_dgamma else None
+    dbeta = torch.empty(Kc, C, dtype=torch.float32, device=dev) if want_dbeta else None
+    q = torch.empty(C, dtype=torch.float32, device=dev)
+    r = torch.empty(C, dtype=torch.float32, device=dev)
+    _call(lib.wc_std_bwd_factor_f64, (_ptr(gsum), _ptr(gxsum), _ptr(mu), _ptr(w), _ptr(gamma), int(M), C, Kc, int(bool(training)),
+                                      _ptr(dgamma), _ptr(dbeta), _ptr(q), _ptr(r)), "wc_std_bwd_factor_f64")
+    return dgamma, dbeta, q, r
+
+
+def std_bwd_apply(x, gy, a, b, q, r, slot=None, relu=False):
+    """dx = a[slot] g' + q x + r, g' = gy masked by the recomputed forward (relu)."""
+    lib = _lib.load()
+    _need(x, torch.float32, "x")
+    _need(gy, torch.float32, "gy")
+    if gy.shape != x.shape:
+        raise ValueError("gy must have x's shape")
+    N, HW, C = _nhwc(x.shape)
+    _need_vec(a, "a", C)
+    _need_vec(b, "b", C, a.shape[0])
+    _need(q, torch.float32, "q", 1)
+    _need(r, torch.float32, "r", 1)
+    if q.numel() != C or r.numel() != C:
+        raise ValueError("q, r must hold C entries")
+    if slot is not None:
+        _need(slot, torch.int32, "slot", 1)
+        if slot.shape[0] != N:
+            raise ValueError("slot must hold one entry per sample")
+    dx = torch.empty_like(x)
+    _call(lib.wc_std_bwd_apply_f32, (_ptr(x), _ptr(gy), _ptr(a), _ptr(b), _ptr(q), _ptr(r), _ptr(slot), N, HW, C, a.shape[0],
+                                     int(bool(relu)), _ptr(dx)),
+          "wc_std_bwd_apply_f32", "wc_std_bwd_apply_f32", "std_apply_kernel", (x, gy, a, b, q, r, slot, dx))
+    return dx

@@ -420,6 +420,17 @@ CONFIGS = {'cifar10_uncond': CIFAR10_UNCOND, 'cifar10_cond': CIFAR10_COND, 'stl1
            'tinyimagenet_cond_sa': TINYIMAGENET_COND_SA}
 
 
+def baseline_config(config, after_norm='ucs', fused=True):
+    """The batch-norm generator the reference sets WC against (run.py:277,285: norm 'b' is its default, after-norm 'ucs'; 'ccs' is the
+    conditional batch norm of the cWC comparisons): a copy of a CONFIGS entry with both norms 'b', both after-norms `after_norm`, on
+    the fused HIP route (fused=False: torch's BatchNorm2d and the coloring branches one by one).  The entry itself is left alone."""
+    import copy
+    out = copy.deepcopy(config)
+    out['generator'].update(block_norm='b', last_norm='b', block_after_norm=after_norm, last_after_norm=after_norm,
+                            fused_batch_norm=bool(fused))
+    return out
+
+
 def wc_sites(config, batch):
     """(name, N, H, W, C) of every WC site of the config's generator at batch size `batch` (bn1 on the
     block input, bn2 after the upsampling conv1, then the final site generator.py:154)."""
