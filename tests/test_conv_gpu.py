@@ -42,7 +42,7 @@ CASES = [
     ('down', 32, 12, 12, 128, 256, 0, True),
     ('up', 2, 8, 8, 128, 128, 0, True),
     ('up', 32, 4, 4, 256, 256, 0, True),
-    ('same', 128, 16, 16, 256, 256, 3, True),        # the 256-point tile
+    ('same', 128, 16, 16, 256, 256, 3, True),        # 128-point tile <2,4>: only 128 tiles of 256 points (test_conv_dispatch_gpu.py has the 256-point tile)
     ('up', 8, 6, 6, 256, 256, 0, False),             # 288 points: not a multiple of the 128-point tile
     ('same', 2, 8, 8, 32, 128, 3, False),            # the data gradient would produce 32 channels
 ]
