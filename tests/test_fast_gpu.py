@@ -177,7 +177,7 @@ def test_bwd_reduce_with_the_relu_mask_in_its_staging(ops, shape, Kc):
 
 
 # ---- fast reductions (wc_fast_xty.hip) -------------------------------------------------------------------------
-XTY_CASES = [((16, 32, 32, 256), 1), ((128, 32, 32, 256), 1), ((32, 32, 32, 128), 1), ((16, 64, 64, 64), 1), ((8, 64, 64, 32), 1)]
+XTY_CASES = [((20, 32, 32, 256), 1), ((128, 32, 32, 256), 1), ((32, 32, 32, 128), 1), ((16, 64, 64, 64), 1), ((8, 64, 64, 32), 1)]
 
 
 @pytest.mark.parametrize("shape,_k", XTY_CASES)
