@@ -748,6 +748,38 @@ int    wc_bwd_factor_zca_f64(const double* R, const double* gsum, const double* 
                              float* S /*[C,C]*/, float* gmean /*[C]*/,
                              void* ws, size_t ws_bytes, wc_stream_t stream);
 
+/* ==== norm 'dr': renorm whitening, DecorelationNormalization(renorm=True) ==================================================
+ * Additive like the entries above: WC_CORE_API keeps its list and WC_ABI_VERSION its value.  In training mode a renorm site whitens with
+ *     W_eff = W_m sg(L) W,    L L^T = (1 - eps) Sigma_batch + eps I,  W = L^-1  (K2, unchanged),
+ *                              L_m L_m^T = (1 - eps) moving_cov + eps I,  W_m = L_m^-1  (the moving statistics BEFORE this call's update)
+ * whose value is W_m and whose gradient reaches x through W alone; C0 = W_m L (lower triangular) is a constant of the step.  The forward
+ * colours with W_m in W's place (no C0 there); K5 takes W_m in dgamma and C0^T in front of its chain.  K1, K3, K4, K6 are untouched.
+ * Widths: C % 32 == 0, 32 <= C <= 1024 (wc_renorm_supported; WC_ERR_CHANNELS otherwise). */
+
+/* The moving factor and C0, float64, full matrices with exact zeros above the diagonal.  Two phases, selected by the nullable inputs, so
+ * that a site can take the moving factor BEFORE K2 updates moving_cov in place and the product after K2 made L:
+ *     moving_cov != NULL:  W_m <- inverse of the Cholesky factor of (1 - eps) moving_cov + eps I -- K2's evaluation-mode launches themselves
+ *                          (bit for bit the W of wc_factor_f64 with training == 0)
+ *     L != NULL:           C0 <- W_m L  (W_m as just computed, or as given when moving_cov == NULL); tiles above the diagonal are skipped
+ *                          and k runs over the block columns j..i only (v_mfma_f64_16x16x4_f64)
+ * At least one of the two must be given; C0 may be NULL when L is.  Stream-ordered, graph-capturable, allocates nothing. */
+int    wc_renorm_supported(int C);
+size_t wc_renorm_workspace_bytes(int C);
+int    wc_renorm_f64(const float* moving_cov /*[C,C], nullable*/, const double* L /*[C,C], nullable*/, int C, double eps,
+                     double* Wm /*[C,C] out (in when moving_cov == NULL)*/, double* C0 /*[C,C] out*/,
+                     void* ws, size_t ws_bytes, wc_stream_t stream);
+
+/* K5 of a renorm site: wc_bwd_factor_f64 with
+ *     dgamma[k] = W_m R[k];   Wbar_eff = sum_k Gamma_k R_k^T;   P = -Phi(C0^T Wbar_eff W^T);   S = 2 (1 - eps) / (M - ddof) sym(W^T P W)
+ * gmean and dbeta as there (A is the site's A_k = W_m^T Gamma_k).  training == 0: dgamma and dbeta only, S and gmean untouched. */
+size_t wc_bwd_factor_renorm_workspace_bytes(int C, int Kc);
+int    wc_bwd_factor_renorm_f64(const double* R, const double* gsum, const double* W, const double* Wm, const double* C0,
+                                const float* gamma, const float* A, int Kc, int C, int64_t M,
+                                double eps, int ddof, int training,
+                                float* dgamma /*[Kc,C,C]*/, float* dbeta /*[Kc,C]*/,
+                                float* S /*[C,C]*/, float* gmean /*[C]*/,
+                                void* ws, size_t ws_bytes, wc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

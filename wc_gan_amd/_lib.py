@@ -172,6 +172,13 @@ SIGNATURES = {
     "wc_bwd_factor_zca_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64,
                                       c_double, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_size_t, c_void_p]),
+    "wc_renorm_supported": (c_int, [c_int]),
+    "wc_renorm_workspace_bytes": (c_size_t, [c_int]),
+    "wc_renorm_f64": (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wc_bwd_factor_renorm_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "wc_bwd_factor_renorm_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64,
+                                         c_double, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_size_t, c_void_p]),
 }
 
 

@@ -1152,6 +1152,41 @@ int wc_bwd_factor_zca_f64(const double* R, const double* gsum, const double* W, 
     return WC_OK;
 }
 
+// K5 of a renorm site.  W_eff = W_m sg(L) W = C0 W with C0 = W_m L constant: the coloring sees W_m
+// (dgamma[k] = W_m R[k], Wbar_eff = sum_k Gamma_k R_k^T) and the batch factor receives Wbar = C0^T Wbar_eff -- K5's short form
+// P = -Phi(Wbar W^T) with one triangular product in front (C0^T is upper triangular: k runs from the diagonal on).
+size_t wc_bwd_factor_renorm_workspace_bytes(int C, int Kc) { return wc_bwd_factor_workspace_bytes(C, Kc); }
+
+int wc_bwd_factor_renorm_f64(const double* R, const double* gsum, const double* W, const double* Wm, const double* C0,
+                             const float* gamma, const float* A, int Kc, int C, int64_t M, double eps, int ddof, int training,
+                             float* dgamma, float* dbeta, float* S, float* gmean,
+                             void* ws, size_t ws_bytes, wc_stream_t stream)
+{
+    if (!R || !gsum || !Wm || !ws) return WC_ERR_NULL;
+    if (training && (!W || !C0 || !A || !S || !gmean)) return WC_ERR_NULL;
+    if (bad_channels(C)) return WC_ERR_CHANNELS;
+    if (Kc <= 0 || (!gamma && Kc != 1) || (training && M <= ddof)) return WC_ERR_SHAPE;
+    if (!(eps > 0.0) || eps >= 1.0 || ddof < 0 || ddof > 1) return WC_ERR_ARG;
+    if (ws_bytes < wc_bwd_factor_renorm_workspace_bytes(C, Kc)) return WC_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t CC = (int64_t)C * C;
+    Carver cv(ws, ws_bytes);
+    double* buf0 = cv.take<double>(CC);
+    double* buf1 = cv.take<double>(CC);
+    double* buf2 = cv.take<double>(CC);
+
+    const double* Wbar = nullptr; int64_t wb_rs = 0, wb_cs = 0; bool done = false;
+    const int rc = k5_head(R, gsum, Wm, gamma, Kc, C, training, dgamma, dbeta, cv, buf0, st, &Wbar, &wb_rs, &wb_cs, &done);
+    if (rc != WC_OK || done) return rc;
+    WC_TRY(wc_launch_tri_gemm(1, C0, 1, C, Wbar, wb_rs, wb_cs, buf2, C, st));                                   // C0^T Wbar_eff
+    WC_TRY(wc_launch_gemm(k5_gemm(C, buf2, 0, C, 1, W, 0, 1, C, buf1, 0, -1.0, WC_EPI_PHI), st));              // P = -Phi((.) W^T)
+    WC_TRY(wc_launch_gemm(k5_gemm(C, W, 0, 1, C, buf1, 0, C, 1, buf2, 0, 1.0, WC_EPI_NONE), st));              // Q1 = W^T P
+    WC_TRY(wc_launch_gemm(k5_gemm(C, buf2, 0, C, 1, W, 0, C, 1, buf0, 0, 1.0, WC_EPI_NONE), st));              // Q2 = Q1 W
+    const double scale = 2.0 * (1.0 - eps) / (double)(M - ddof);
+    WC_TRY(wc_launch_bwd_tail(buf0, C, scale, S, gsum, A, Kc, M, gmean, dbeta, st));      // S, gmean, dbeta
+    return WC_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 size_t wc_bwd_apply_workspace_bytes(int64_t N, int64_t HW, int C, int Kc)
 {

@@ -309,6 +309,11 @@ hipError_t wc_launch_gemm(const WcGemm& g, hipStream_t st);
 hipError_t wc_launch_sum_partials(const double* part, int nparts, int64_t n, double* out, hipStream_t st);      // out[e] = sum_p part[p][e], fixed order
 hipError_t wc_launch_gemm_pair_dd_fd(const WcGemm& g0, const WcGemm& g1, hipStream_t st);      // two independent products (double x double, float x double) in one launch
 
+// triangular products (wc_renorm.hip), row-major C x C doubles out, element strides in: upper == 0: A, B lower -> Cm lower (its upper
+// triangle exact zeros), k over j..i only; upper != 0: A upper, B general, k over i.. only
+hipError_t wc_launch_tri_gemm(int upper, const double* A, int64_t a_rs, int64_t a_cs, const double* B, int64_t b_rs, int64_t b_cs,
+                              double* Cm, int C, hipStream_t st);
+
 hipError_t wc_launch_transpose_to_f32(const double* W, int C, int groups, float* A, float* At, hipStream_t st);  // A = W^T, At = W
 hipError_t wc_launch_group_bias(const float* mu, const float* A, const float* beta, int G, int Kc, int C, int per_group,
                                 float* center, float* bias, hipStream_t st, const float* center_in = nullptr /*given: the common centre (center is not written)*/);

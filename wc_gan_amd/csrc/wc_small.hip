@@ -283,7 +283,7 @@ __global__ void factor_prepare_kernel(const double* __restrict__ sum, const doub
             }
         } else {
             sig = 0.5 * ((double)moving_cov[e] + (double)moving_cov[(int64_t)j * C + i]);
-            if (i == 0) mu[(int64_t)g * C + j] = moving_mean[j];
+            if (i == 0 && mu) mu[(int64_t)g * C + j] = moving_mean[j];      // (mu == NULL: the moving factor alone, wc_renorm_f64)
         }
         const double t = (1.0 - eps) * sig + (i == j ? eps : 0.0);
         // lower_only: the fused Cholesky reads block rows at and below the diagonal only and leaves the rest as it finds

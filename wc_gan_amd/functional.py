@@ -123,7 +123,7 @@ def _bwd_reduce(x, xs, mu, gy, y, slot, Kc, relu, bits, share, flat):
 class WhitenColorFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, slot, moving_mean, moving_cov, training, eps, momentum, ddof, process_group, relu=False,
-                handoff=False, st=None, decomposition='cholesky'):
+                handoff=False, st=None, decomposition='cholesky', renorm=False):
         # x: (N, ..., C) float32 contiguous (NHWC); gamma (Kc,C,C)|None; beta (Kc,C)|None; slot int32 (N,)|None
         # handoff: the output leaves as the next convolution's fp16 planes (the K3 -> convolution hand-off below): y is a handle carrying them
         # st: x is a HANDLE whose data is this ops.SplitTensor (the residual add wrote the pre-split planes, split_handle below):
@@ -135,17 +135,27 @@ class WhitenColorFunction(torch.autograd.Function):
             x = x.contiguous()
         # decomposition='zca': `L` below is the eigen-stage's (U, lam); everything behind W is the Cholesky site's
         zca = decomposition == 'zca'
+        # renorm (norm 'dr', training mode): the moving factor W_m first -- K2 below updates moving_cov in place and the renormalised
+        # whitening is defined on the statistics from before the update
+        renorm = bool(renorm) and bool(training)
+        Wm = ops.renorm(moving_cov, None, eps)[0] if renorm else None
         mu, L, W, chan_scale = _whiten(x, st, training, eps, momentum, ddof, moving_mean, moving_cov, process_group, 1, decomposition)
         lam_t = ()
         if zca:
             L, lam_t = L[0], (L[1],)
+        Wc = W                  # the matrix the coloring folds in
+        if renorm:
+            # W_eff = W_m sg(L) W: the value is W_m's, so the coloring takes W_m; C0 = W_m L stands where L does (K5 reads it, with W
+            # and W_m).  Under sync-WC L is the factor of the all-reduced moments: every rank whitens with the same W_m (x - mu)
+            L = ops.renorm(None, L, eps, Wm)[1]
+            Wc, lam_t = Wm, (Wm,)
         g = gamma.contiguous() if gamma is not None else None
         b = beta.contiguous() if beta is not None else None
         bias = b
         if st is not None:      # ... and, on planes, the additive term beta + (center - mu) A from the same launch as the tables
-            A, At, plan, bias = ops.color_split(W, g, st, mu, b)
+            A, At, plan, bias = ops.color_split(Wc, g, st, mu, b)
         else:
-            A, At, plan = ops.color(W, g, chan_scale)      # plan: the apply's fp16 tables, so K3 is one launch
+            A, At, plan = ops.color(Wc, g, chan_scale)      # plan: the apply's fp16 tables, so K3 is one launch
         # relu: folded into K3's epilogue (row N2).  Its gradient mask is kept as ONE BIT per element (K3 writes it): the
         # backward neither re-reads y (K4: 134 MB at the headline site) nor keeps y alive for it
         bits = bool(relu) and M_local % 32 == 0
@@ -168,7 +178,8 @@ class WhitenColorFunction(torch.autograd.Function):
         ctx.save_for_backward(x, mu, L, W, A, At, g if g is not None else torch.empty(0, device=dev),
                               slot if slot is not None else torch.empty(0, dtype=torch.int32, device=dev),
                               mask if bits else (y if relu else torch.empty(0, device=dev)), *xs_t, *lam_t)
-        ctx.zca, ctx.lam_at = zca, 9 + len(xs_t)          # (saved_tensors: the nine above, the planes' three where K4 / K6 read them, then lam)
+        # (saved_tensors: the nine above, the planes' three where K4 / K6 read them, then ZCA's lam or renorm's W_m)
+        ctx.zca, ctx.renorm, ctx.lam_at = zca, renorm, 9 + len(xs_t)
         ctx.relu = bool(relu)
         ctx.mask_bits = bits
         ctx.has_gamma = g is not None
@@ -192,6 +203,11 @@ class WhitenColorFunction(torch.autograd.Function):
 
             def k5(R, gsum, W, L, *rest, **kw):
                 return ops.bwd_factor_zca(R, gsum, W, U, lam, *rest, **kw)
+        elif ctx.renorm:    # ... and a renorm site's takes W_m and C0 = W_m L (saved in L's place)
+            Wm = ctx.saved_tensors[ctx.lam_at]
+
+            def k5(R, gsum, W, C0, *rest, **kw):
+                return ops.bwd_factor_renorm(R, gsum, W, Wm, C0, *rest, **kw)
         else:
             k5 = ops.bwd_factor
         need_x, need_g, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
@@ -229,7 +245,7 @@ class WhitenColorFunction(torch.autograd.Function):
                     if k6_mask is not None:
                         gy, k6_mask = ops.relu_mask_bits(gy, k6_mask), None
                 dx = ops.bwd_apply(gy, x, mu, At, S, gmean, slot, scales=scales, relu_mask=k6_mask)
-        return dx, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None, None
+        return dx, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 # ---------------------------------------------------------------------------------------------
@@ -428,18 +444,25 @@ def whiten_color_eval_cached(x, cache, gamma=None, beta=None, slot=None, moving_
 
 
 def whiten_color(x, gamma=None, beta=None, slot=None, moving_mean=None, moving_cov=None, training=True,
-                 eps=1e-3, momentum=0.99, ddof=1, process_group=None, relu=False, planes=False, decomposition='cholesky'):
+                 eps=1e-3, momentum=0.99, ddof=1, process_group=None, relu=False, planes=False, decomposition='cholesky', renorm=False):
     """y = coloring(whitening(x)) (relu=True: max(y, 0) from the same kernel).  x: (N, H, W, C) float32 on the GPU,
     C % 32 == 0 (see layers for padding).  planes=True (relu'd sites whose consumer is conv.fast_conv): where K3 can, the
     result is a HANDLE -- a NaN tensor of y's shape without memory that carries the autograd edge -- with the output itself
     attached as the convolution's fp16 planes (handle._wc_planes); else the plain tensor.
-    decomposition: 'cholesky' (W = L^-1) or 'zca' (W = U diag(lam^-1/2) U^T of Sigma + eps I; C <= 256, ops.zca_supported)."""
+    decomposition: 'cholesky' (W = L^-1) or 'zca' (W = U diag(lam^-1/2) U^T of Sigma + eps I; C <= 256, ops.zca_supported).
+    renorm (norm 'dr', Cholesky only): in training mode the whitening is W_m sg(L) W -- the value is that of the moving statistics as they
+    were before this call, W_m (x - mu_batch), the gradient flows through the batch factor (ops.renorm, ops.bwd_factor_renorm); no effect
+    in evaluation mode."""
     if decomposition not in ('cholesky', 'zca'):
         raise ValueError(f"unknown decomposition {decomposition!r}")
+    if renorm and decomposition != 'cholesky':
+        raise NotImplementedError("renorm is defined for decomposition='cholesky' only")
+    if renorm and training and moving_cov is None:
+        raise ValueError("renorm whitens with the moving statistics: moving_cov is required")
     handoff = planes and conv_handoff_supported(x.shape, relu, 1 if gamma is None else gamma.shape[0])
     return WhitenColorFunction.apply(x, gamma, beta, slot, moving_mean, moving_cov, bool(training),
                                      float(eps), float(momentum), int(ddof), process_group, bool(relu), bool(handoff), split_of(x),
-                                     decomposition)
+                                     decomposition, bool(renorm))
 
 
 _ROUTE = {}

@@ -199,24 +199,23 @@ class DecorelationNormalization(_Lazy):
                 self._eval_plan = WF.EvalPlan()
             return WF.whiten_color_eval_cached(x, self._eval_plan, gamma, beta, slot, self.moving_mean, self.moving_cov,
                                                self.epsilon, gamma_key, relu=relu, planes=planes, decomposition=dec)
-        if self.renorm and self.training:
-            gamma = self._renorm_gamma(x, gamma)
         if USE_TORCH_OPS and self.process_group is None and dec == 'cholesky':
             # the same site through the registered operator torch.ops.wc.whiten_color (torch_ops.py: schema, fake kernel,
             # autograd formula on the op) -- what torch.compile / FX tooling see; no hand-off, no bit mask on this route
             from . import torch_ops
+            if self.renorm and self.training:       # (the operator's schema has no renorm: folded into the coloring in front of it)
+                gamma = self._renorm_gamma(x, gamma)
             return torch_ops.whiten_color_site(x, gamma, beta, slot, self.moving_mean, self.moving_cov, self.training,
                                                self.epsilon, self.momentum, 1, relu)
         return WF.whiten_color(x, gamma, beta, slot, self.moving_mean, self.moving_cov, self.training,
-                               self.epsilon, self.momentum, 1, self.process_group, relu=relu, planes=planes, decomposition=dec)
+                               self.epsilon, self.momentum, 1, self.process_group, relu=relu, planes=planes, decomposition=dec,
+                               renorm=self.renorm)
 
     def takes_split(self, shape):
         """Can this layer, in its present mode, read an input of this NHWC shape as pre-split planes (the residual add in front then
         writes those instead of fp32: functional.residual_add)?  The fused route only (either decomposition), C in {128, 256}, the shapes of
         functional.split_route_supported."""
         if self.channels is None or self.channels != shape[-1] or not self._fused_width(shape[-1]) or USE_TORCH_OPS:
-            return False
-        if self.renorm and self.training:
             return False
         groups = _stat_groups() if self.training else 1
         if groups > 1 and self.process_group is not None:
@@ -226,6 +225,7 @@ class DecorelationNormalization(_Lazy):
         return WF.split_route_supported(tuple(shape), self.training, groups)
 
     def _renorm_gamma(self, x, gamma):
+        # (the WC_TORCH_OPS=1 route only: the fused route takes renorm itself, functional.whiten_color(renorm=True))
         # W_eff = L_mov^-1 . stop_grad(L_batch) . L_batch^-1 (row a4): the batch factor carries the gradient,
         # the value is the moving-statistics whitening.  Folded into the coloring: Gamma' = (L_mov^-1 L_batch)^T Gamma.
         C = self.channels
@@ -242,14 +242,17 @@ class DecorelationNormalization(_Lazy):
         return torch.matmul(C0t.unsqueeze(0), gamma)
 
     def _padded(self, x, gamma, beta, slot):
-        # zero channels whiten to zero and leave the real channels' Cholesky rows untouched; ZCA of a block-diagonal covariance is
+        # zero channels whiten to zero and leave the real channels' Cholesky rows untouched (renorm: the padded moving covariance is
+        # block-diagonal as well, so W_m and C0 = W_m L are, and the real channels see their own blocks); ZCA of a block-diagonal covariance is
         # block-diagonal too (the padded channels are an exactly degenerate eigenvalue eps: the closed-form backward is finite there)
         C = self.channels
         xp, _ = _pad_channels(x)
         Cp = xp.shape[-1]
-        if self.renorm or not self._fused_width(Cp):
-            raise NotImplementedError(f"{self.layer_name}: widths that are not a multiple of 32 are built without renorm only "
-                                      "(and, for decomposition='zca', up to 256 channels)")
+        if not self._fused_width(Cp):
+            raise NotImplementedError(f"{self.layer_name}: widths that are not a multiple of 32 are built, for decomposition='zca', "
+                                      "up to 256 channels only")
+        if self.renorm and self.decomposition != 'cholesky':
+            raise NotImplementedError("renorm is defined for decomposition='cholesky' only")
         with torch.no_grad():
             self._pad_mean.zero_(); self._pad_mean[:C] = self.moving_mean
             self._pad_cov.copy_(self._pad_eye); self._pad_cov[:C, :C] = self.moving_cov
@@ -258,7 +261,7 @@ class DecorelationNormalization(_Lazy):
         g[:, :C, :C] = gamma if gamma is not None else self._pad_eye[:C, :C]
         b = None if beta is None else F.pad(beta, (0, Cp - C))
         y = WF.whiten_color(xp.contiguous(), g, b, slot, self._pad_mean, self._pad_cov, self.training,
-                            self.epsilon, self.momentum, 1, self.process_group, decomposition=self.decomposition)
+                            self.epsilon, self.momentum, 1, self.process_group, decomposition=self.decomposition, renorm=self.renorm)
         with torch.no_grad():
             self.moving_mean.copy_(self._pad_mean[:C]); self.moving_cov.copy_(self._pad_cov[:C, :C])
         return y[..., :C]

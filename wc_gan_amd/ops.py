@@ -811,6 +811,65 @@ def bwd_factor_zca(R, gsum, W, U, lam, gamma, A, M, eps, ddof, training, want_dg
     return dgamma, dbeta, S, gmean
 
 
+def renorm_supported(C):
+    """Widths the renorm stage takes (wc_renorm_supported): K2's, C % 32 == 0, 32 <= C <= 1024."""
+    return bool(_lib.load().wc_renorm_supported(int(C)))
+
+
+def renorm(moving_cov, L, eps, Wm=None):
+    """The C x C stage of a renorm ('dr') site -> (Wm, C0) float64, full matrices with zero upper triangles:
+    Wm = L_m^-1 with L_m L_m^T = (1 - eps) moving_cov + eps I (K2's evaluation-mode kernels, bit for bit) and C0 = Wm L for the batch
+    factor L of K2.  The two halves can be taken apart, because K2 updates moving_cov in place: renorm(moving_cov, None, eps) ->
+    (Wm, None) before K2, renorm(None, L, eps, Wm) -> (Wm, C0) behind it."""
+    lib = _lib.load()
+    if moving_cov is None and L is None:
+        raise ValueError("renorm needs moving_cov, L or both")
+    if moving_cov is not None:
+        _need(moving_cov, torch.float32, "moving_cov", 2)
+        if Wm is not None:
+            raise ValueError("Wm is an input only when moving_cov is None")
+    elif Wm is None:
+        raise ValueError("renorm(None, L, eps) needs the Wm of an earlier call")
+    if L is not None:
+        _need(L, torch.float64, "L", 2)
+    if Wm is not None:
+        _need(Wm, torch.float64, "Wm", 2)
+    ref = moving_cov if moving_cov is not None else L
+    C, dev = ref.shape[-1], ref.device
+    for t in (moving_cov, L, Wm):
+        if t is not None and tuple(t.shape) != (C, C):
+            raise ValueError(f"renorm takes (C, C) matrices of one width, got {tuple(t.shape)}")
+    if Wm is None:
+        Wm = torch.empty(C, C, dtype=torch.float64, device=dev)
+    C0 = torch.empty(C, C, dtype=torch.float64, device=dev) if L is not None else None
+    nb = lib.wc_renorm_workspace_bytes(C)
+    if nb == 0:
+        _lib.check(-3, "wc_renorm_f64")
+    ws = _workspace(nb, dev)
+    _lib.check(lib.wc_renorm_f64(_ptr(moving_cov), _ptr(L), C, float(eps), _ptr(Wm), _ptr(C0), _ptr(ws), ws.numel(), _stream()),
+               "wc_renorm_f64")
+    return Wm, C0
+
+
+def bwd_factor_renorm(R, gsum, W, Wm, C0, gamma, A, M, eps, ddof, training, want_dgamma=True, want_dbeta=True):
+    """K5 of a renorm site: bwd_factor with Wm in dgamma and C0^T in front of the statistics chain -> (dgamma, dbeta, S, gmean)."""
+    lib = _lib.load()
+    Kc, C = R.shape[0], R.shape[1]
+    dev = R.device
+    dgamma = torch.empty(Kc, C, C, dtype=torch.float32, device=dev) if (gamma is not None and want_dgamma) else None
+    dbeta = torch.empty(Kc, C, dtype=torch.float32, device=dev) if want_dbeta else None
+    S = torch.empty(C, C, dtype=torch.float32, device=dev) if training else None
+    gmean = torch.empty(C, dtype=torch.float32, device=dev) if training else None
+    nb = lib.wc_bwd_factor_renorm_workspace_bytes(C, Kc)
+    if nb == 0:
+        _lib.check(-3, "wc_bwd_factor_renorm_f64")
+    ws = _workspace(nb, dev)
+    _lib.check(lib.wc_bwd_factor_renorm_f64(_ptr(R), _ptr(gsum), _ptr(W), _ptr(Wm), _ptr(C0), _ptr(gamma), _ptr(A), Kc, C, int(M),
+                                            float(eps), int(ddof), int(bool(training)), _ptr(dgamma), _ptr(dbeta),
+                                            _ptr(S), _ptr(gmean), _ptr(ws), ws.numel(), _stream()), "wc_bwd_factor_renorm_f64")
+    return dgamma, dbeta, S, gmean
+
+
 def bwd_apply(gy, x, mu, At, S, gmean, slot, fast=True, scales=None, relu_mask=None):
     """K6: dx[n] = gy[n] At[slot[n]] + (x[n]-mu) S - gmean.  scales: the (2C,) input scales bwd_reduce(..., want_scales=True)
     returned for the same x, mu, gy (three launches instead of six).  relu_mask: gy is the gradient BEFORE the site's ReLU and

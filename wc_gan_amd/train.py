@@ -440,6 +440,16 @@ def zca_config(config):
     return out
 
 
+def renorm_config(config):
+    """The same generator with renorm whitening at every WC site (norm 'dr': DecorelationNormalization(renorm=True), generator.py:26):
+    a copy of a CONFIGS entry, the entry itself is left alone.  No shipped configuration uses it.  (A renorm layer has no grouped
+    form: GanTrainer.generate runs separate generator passes for such a generator.)"""
+    import copy
+    out = copy.deepcopy(config)
+    out['generator'].update(block_norm='dr', last_norm='dr')
+    return out
+
+
 def wc_sites(config, batch):
     """(name, N, H, W, C) of every WC site of the config's generator at batch size `batch` (bn1 on the
     block input, bn2 after the upsampling conv1, then the final site generator.py:154)."""
