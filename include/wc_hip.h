@@ -552,7 +552,8 @@ typedef struct {
 
 #define WC_CONV_SCRATCH_BYTES 2048
 
-/* 1 when wc_conv_f16x3 takes the geometry (N*H*W a multiple of 128, channel multiples as above). */
+/* 1 when wc_conv_f16x3 takes the geometry (N*H*W a multiple of 128, Cin a multiple of 32, Cout a multiple of 64: a width that is 64
+ * beyond a multiple of 128 -- the DC critic's 64-filter layers, discriminator.py:41-60 with arch 'dcgan' -- runs 64-output tiles). */
 int wc_conv_supported(const wc_conv_geom* g);
 
 /* hi = fp16(s*x), lo = fp16(s*x - hi) over n floats (n % 4 == 0), s = the power of two that puts max|x| into
@@ -594,6 +595,19 @@ int wc_conv_split_colsum_f32(const float* x, int64_t n, int relu, void* hi, void
 int wc_conv_split_hist_f32(const float* x, int64_t n, int relu, void* hi, void* lo, float* scale, float* colsum_partials /*nullable*/, int C,
                            float* hist, int bootstrap, wc_stream_t stream);
 
+/* LeakyReLU in front of the split (the DC critic's LeakyReLU -> Conv2D pairs, discriminator.py:41-60: Keras's default slope 0.3):
+ * v = x > 0 ? x : negative_slope * x (one fp32 multiply), then the scaling and hi / lo rounding of the entries above.  0 <= slope <= 1
+ * (the measured scale is that of the activated tensor, max|LeakyReLU(x)|); slope 0 takes the ReLU form and gives the bits of relu = 1.
+ * wc_conv_split_leaky_f32 = wc_conv_split_colsum_f32 (colsum_partials nullable), wc_conv_split_hist_leaky_f32 = wc_conv_split_hist_f32
+ * with the same record rules (the record holds the maximum AFTER the activation, as with the ReLU).
+ * wc_conv_leaky_bwd_f32: the activation's backward on the data gradient, in place and in one launch: dx[i] *= x[i] > 0 ? 1 : slope
+ * (torch's convention at 0); n % 4 == 0. */
+int wc_conv_split_leaky_f32(const float* x, int64_t n, float negative_slope, void* hi, void* lo, float* scale, void* amax_scratch,
+                            float* colsum_partials /*nullable*/, int C, wc_stream_t stream);
+int wc_conv_split_hist_leaky_f32(const float* x, int64_t n, float negative_slope, void* hi, void* lo, float* scale,
+                                 float* colsum_partials /*nullable*/, int C, float* hist, int bootstrap, wc_stream_t stream);
+int wc_conv_leaky_bwd_f32(float* dx, const float* x, int64_t n, float negative_slope, wc_stream_t stream);
+
 /* Weight fragment images for a geometry: element (k, n, r, s) of the source is w[k*stride_k + n*stride_n + r*stride_r +
  * s*stride_s] (k = reduction channel, n = output channel of the product), `n_elems` = extent of the source storage (for
  * the tensor scale).  `image`: wc_conv_weights_bytes(g) device bytes.  `known_amax` (nullable): `known_count` device
@@ -619,7 +633,8 @@ int wc_conv_f16x3(const void* xhi, const void* xlo, const float* xscale, const v
                   void* ws, size_t ws_bytes, wc_stream_t stream);
 
 /* Weight gradient of the same convolution: dW(k, n, r, s) = sum over the grid of x[input pixel][k] * gy[output pixel][n]
- * for the FORWARD geometry `g` (x and gy as split planes; Cin and Cout multiples of 128), written to
+ * for the FORWARD geometry `g` (x and gy as split planes; Cin and Cout multiples of 64 -- 64 x 64 tiles when either is no multiple
+ * of 128), written to
  * dw[k*stride_k + n*stride_n + r*stride_r + s*stride_s] (every element of the taps the geometry names; fixed summation
  * order).  `ws`: wc_conv_wrw_workspace_bytes(g) device bytes. */
 size_t wc_conv_wrw_workspace_bytes(const wc_conv_geom* g);
@@ -640,7 +655,16 @@ int    wc_conv_wrw_narrow_f32(const float* x, const float* gy, int64_t N, int64_
                               float* dw, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s, float* db /*nullable*/,
                               void* ws, size_t ws_bytes, wc_stream_t stream);
 
-/* Forward of the same kind of layer (ksize^2 * Cin < 32, Cout a multiple of 128; wc_conv_wrw_narrow_supported):
+/* The same three for Cout a multiple of 64 (the DC critic's first layer, 3 -> 64 at 3x3): a superset -- the entries above keep refusing
+ * what they refused (callers size and gate by them).  A last group of 64 channels runs the 128-channel group with half its lanes idle;
+ * the workspace holds one partial per STARTED 128 channels. */
+int    wc_conv_narrow64_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize);
+size_t wc_conv_wrw_narrow64_workspace_bytes(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize);
+int    wc_conv_wrw_narrow64_f32(const float* x, const float* gy, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize,
+                                float* dw, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s, float* db /*nullable*/,
+                                void* ws, size_t ws_bytes, wc_stream_t stream);
+
+/* Forward of the same kind of layer (ksize^2 * Cin < 32, Cout a multiple of 64; wc_conv_narrow64_supported):
  *     y[p][o] = bias[o] + sum_{r,s,c} x[p + (r, s) - pad][c] w[c*stride_k + o*stride_n + r*stride_r + s*stride_s]      (relu != 0: max(., 0))
  * in one launch on the fp32 matrix pipe, the bias as a row of the product (bias nullable).  The strides may be negative: with x := gy of a layer
  * with a handful of OUTPUT channels, stride_k / stride_n exchanged and the tap strides negated (w pointing at its last tap) this is that

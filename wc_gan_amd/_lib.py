@@ -135,6 +135,13 @@ SIGNATURES = {
     "wc_spectral_norm_amax_offset": (c_size_t, [c_int, c_int]),
     "wc_spectral_norm_error_offset": (c_size_t, [c_int, c_int]),
     "wc_conv_split_hist_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "wc_conv_split_leaky_f32": (c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "wc_conv_split_hist_leaky_f32": (c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "wc_conv_leaky_bwd_f32": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p]),
+    "wc_conv_narrow64_supported": (c_int, [c_int64, c_int64, c_int64, c_int, c_int, c_int]),
+    "wc_conv_wrw_narrow64_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int, c_int, c_int]),
+    "wc_conv_wrw_narrow64_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_int64, c_int64,
+                                         c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "wc_conv_fwd_narrow_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int,
                                        c_int, c_void_p, c_void_p]),
     "wc_conv_wrw_narrow_supported": (c_int, [c_int64, c_int64, c_int64, c_int, c_int, c_int]),

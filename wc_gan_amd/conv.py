@@ -10,7 +10,8 @@
 
 Forward and the data gradient run on the HIP kernel (the data gradient of 'same' is a 'same', of 'down' an 'up' and of
 'up' a 'down', with the channel roles swapped in the weight image), and so does the weight gradient (pixel-major tiles
-read back through gfx950's transposing LDS read).  No fallback inside: `supported(...)` tells the caller whether the kernel takes a shape.
+read back through gfx950's transposing LDS read).  `relu_input` / `leaky_input` (fast_conv_or_none): the layer is conv(relu(x)) /
+conv(leaky_relu(x, slope)) and the activation happens while x is split.  Channel widths: multiples of 128, of 64 for 'down'.  No fallback inside: `supported(...)` tells the caller whether the kernel takes a shape.
 """
 from __future__ import annotations
 
@@ -99,7 +100,7 @@ def _supported(g):
 
 
 def supported(x, w, kind):
-    """Does the kernel take this call?  (channels multiples of 128, N*H*W of the virtual grid a multiple of 128)"""
+    """Does the kernel take this call?  (channels multiples of 128 -- of 64 for kind 'down' --, N*H*W of the virtual grid a multiple of 128)"""
     handed = getattr(x, '_wc_planes', None) is not None       # a K3 handle: the data is in the planes it carries
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and (handed or x.is_contiguous()) and w.dtype == torch.float32):
         return False
@@ -140,6 +141,11 @@ def _plan(kind, x, w):
                (kind == 'up' and w.shape[0] == C and tuple(w.shape[2:]) == (4, 4))
         if kind not in ('same', 'down', 'up', 'down3', 'up3'):
             raise ValueError(kind)
+        # A width that is 64 beyond a multiple of 128 (the kernels' 64-wide tiles): the layer entry takes it for the plain 4x4 stride-2
+        # convolution only -- the DC critic's 64 -> 128 layer.  The kernels take every geometry with such a width (_Plan.ok says so, and
+        # tests/test_dcgan_conv_gpu.py runs them); the 64-wide ResNet blocks of toy configurations stay on their other path, as before.
+        if good and kind != 'down' and (C % 128 or w.shape[0] % 128 or w.shape[1] % 128):
+            good = False
         p = _plans[key] = _Plan(kind, N, H, W, tuple(w.shape)) if good else False
     return p
 
@@ -183,11 +189,16 @@ def _site_hist(site, role, device):
     return h
 
 
-def split_planes(x, relu=False, colsum=False, site=None, role='x'):
+def split_planes(x, relu=False, colsum=False, site=None, role='x', leaky=None):
     """fp32 tensor -> (hi, lo, scale): fp16 planes of s*x and the device scalar s.  colsum: also the 512 partial rows of the
     column sums over the last axis (-> the bias gradient, finished by weight_gradient), returned as a 4th element.
-    site (+ role): the layer object this tensor belongs to -- the scale then comes from the previous call of that site (one launch)."""
+    site (+ role): the layer object this tensor belongs to -- the scale then comes from the previous call of that site (one launch).
+    leaky: a negative slope in [0, 1] -- the planes are of LeakyReLU(x) (x > 0 ? x : slope * x); slope 0 gives the bits of relu=True."""
     lib = _lib.load()
+    if leaky is not None:
+        if relu:
+            raise ValueError("relu and leaky are two activations")
+        return _split_planes_leaky(lib, x, float(leaky), colsum, site, role)
     both = torch.empty((2,) + tuple(x.shape), dtype=torch.float16, device=x.device)
     hi, lo = both[0], both[1]
     scale = torch.empty(1 + 512, dtype=torch.float32, device=x.device)    # [scale | per-workgroup maxima scratch]
@@ -208,6 +219,32 @@ def split_planes(x, relu=False, colsum=False, site=None, role='x'):
     _lib.check(lib.wc_conv_split_colsum_f32(_ptr(x), x.numel(), 1 if relu else 0, _ptr(hi), _ptr(lo), _ptr(scale),
                                             scale.data_ptr() + 4, _ptr(part), C, _stream()), "wc_conv_split_colsum_f32")
     return hi, lo, scale, part
+
+
+def _split_planes_leaky(lib, x, slope, colsum, site, role):
+    both = torch.empty((2,) + tuple(x.shape), dtype=torch.float16, device=x.device)
+    hi, lo = both[0], both[1]
+    scale = torch.empty(1 + 512, dtype=torch.float32, device=x.device)
+    C = x.shape[-1]
+    part = torch.empty((512, C), dtype=torch.float32, device=x.device) if colsum else None
+    h = _site_hist(site, role, x.device) if (SPLIT_HIST and site is not None) else None
+    if h is not None:
+        _lib.check(lib.wc_conv_split_hist_leaky_f32(_ptr(x), x.numel(), slope, _ptr(hi), _ptr(lo), _ptr(scale), _ptr(part), C if colsum else 0,
+                                                    _ptr(h[0]), (0 if h[1] else 1) | (0 if _guarded(role) else 2), _stream()),
+                   "wc_conv_split_hist_leaky_f32")
+        h[1] = True
+    else:
+        _lib.check(lib.wc_conv_split_leaky_f32(_ptr(x), x.numel(), slope, _ptr(hi), _ptr(lo), _ptr(scale), scale.data_ptr() + 4,
+                                               _ptr(part), C if colsum else 0, _stream()), "wc_conv_split_leaky_f32")
+    return (hi, lo, scale, part) if colsum else (hi, lo, scale)
+
+
+def leaky_backward_(dx, x, slope):
+    """dx *= (x > 0 ? 1 : slope) in place, one launch (wc_conv_leaky_bwd_f32): the LeakyReLU of conv(leaky(x)) on the data gradient"""
+    if not (dx.is_contiguous() and x.is_contiguous() and dx.shape == x.shape and dx.dtype == x.dtype == torch.float32):
+        raise ValueError("leaky_backward_: dense fp32 tensors of one shape")
+    _lib.check(_lib.load().wc_conv_leaky_bwd_f32(_ptr(dx), _ptr(x), dx.numel(), float(slope), _stream()), "wc_conv_leaky_bwd_f32")
+    return dx
 
 
 def _storage_extent(w):
@@ -330,20 +367,21 @@ def takes_planes(shape, wshape, kind):
 
 class _FastConv(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, bias, kind, plan, relu_input=False, handed=None, site=None):
+    def forward(ctx, x, w, bias, kind, plan, relu_input=False, handed=None, site=None, leaky=None):
         gf, kf, nf = plan.fwd
         # handed: x is a K3 handle and these are its planes (already ReLU'd and split by K3's epilogue: no pass here)
         # relu_input: the layer is conv(relu(x)); the ReLU happens in the split
         # site: the layer object (generator.Conv2D) -- its splits take their scale from the site's previous call (split_planes)
-        planes = handed if handed is not None else split_planes(x, relu=relu_input, site=site, role='x')
-        ctx.site = site
+        # leaky: the layer is conv(leaky_relu(x, leaky)); the activation happens in the split, as the ReLU does
+        planes = handed if handed is not None else split_planes(x, relu=relu_input, site=site, role='x', leaky=leaky)
+        ctx.site, ctx.leaky = site, leaky
         if ctx.needs_input_grad[0]:                 # the data gradient will want its image too: both in one launch
             img, ctx.bwd_image = weight_image_pair(w, plan.fwd, plan.bwd)
         else:
             img, ctx.bwd_image = weight_image(w, gf, kf, nf), None
         y = run(planes, img, gf, bias, nbytes=plan.fwd_ws)
         # the planes stand in for (relu of) x (same bytes) in the weight gradient; x itself only for the ReLU mask
-        ctx.save_for_backward(w, *planes, *((x,) if relu_input else ()))
+        ctx.save_for_backward(w, *planes, *((x,) if (relu_input or leaky is not None) else ()))
         ctx.kind, ctx.has_bias, ctx.plan, ctx.relu_input = kind, bias is not None, plan, relu_input
         return y
 
@@ -362,6 +400,8 @@ class _FastConv(torch.autograd.Function):
             dx = run(g_planes[:3], image, gb, nbytes=plan.bwd_ws)
             if ctx.relu_input:
                 dx = torch.ops.aten.threshold_backward(dx, ctx.saved_tensors[4], 0)
+            elif ctx.leaky is not None:
+                dx = leaky_backward_(dx, ctx.saved_tensors[4], ctx.leaky)
         if ctx.needs_input_grad[1]:
             gf, kf, nf = plan.fwd
             if fused_db:
@@ -370,7 +410,7 @@ class _FastConv(torch.autograd.Function):
                 dw = weight_gradient((xh, xl, xs), g_planes, gf, w, kf, nf, nbytes=plan.wrw_ws)
         if want_db and not fused_db:
             db = gy.sum((0, 1, 2))
-        return dx, dw, db, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None
 
 
 _ones = {}
@@ -448,19 +488,23 @@ def split_conv(x, st, w, bias=None, site=None):
     return _SplitConv.apply(x, w, bias, p, st, site)
 
 
-def fast_conv_or_none(x, w, bias=None, kind='same', relu_input=False, site=None):
+def fast_conv_or_none(x, w, bias=None, kind='same', relu_input=False, site=None, leaky_input=None):
     """fast_conv when the kernel takes the call, else None (the caller's other path).  relu_input: conv(relu(x)).
+    leaky_input: a negative slope -- conv(leaky_relu(x, slope)).
     site: the layer object that owns this convolution (split_planes keeps the splits' scale history there)."""
+    if leaky_input is not None and relu_input:
+        raise ValueError("relu_input and leaky_input are two activations")
     handed = getattr(x, '_wc_planes', None)
     if not supported(x, w, kind):
         if handed is not None:
             raise _lib.WcHipError(f"fast_conv: a K3 handle reached a convolution that cannot take planes {tuple(x.shape)} x {tuple(w.shape)} ({kind})")
         return None
     if handed is not None:
-        if relu_input:
+        if relu_input or leaky_input is not None:
             raise ValueError("a K3 handle is already ReLU'd")
         return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w), False, handed, site)
-    return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w), relu_input, None, site)
+    return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w), relu_input, None, site,
+                           None if leaky_input is None else float(leaky_input))
 
 
 # The critic's first block reads images (Conv2D 3 -> 128 and the 1x1 shortcut 3 -> 128): the forward stays with MIOpen, the weight and bias
@@ -469,14 +513,14 @@ NARROW_WRW = os.environ.get('WC_NARROW_WRW', '1') != '0'
 
 
 def narrow_wrw_supported(x, w):
-    """x NHWC fp32 on the GPU, w (Cout, Cin, k, k) with k in (1, 3), k*k*Cin < 32, Cout a multiple of 128"""
+    """x NHWC fp32 on the GPU, w (Cout, Cin, k, k) with k in (1, 3), k*k*Cin < 32, Cout a multiple of 64"""
     if not (NARROW_WRW and x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32 and x.dim() == 4 and w.dim() == 4):
         return False
     k = w.shape[2]
     if w.shape[3] != k or k not in (1, 3) or w.shape[1] != x.shape[3]:
         return False
     N, H, W, C = x.shape
-    return bool(_lib.load().wc_conv_wrw_narrow_supported(N, H, W, C, w.shape[0], k))
+    return bool(_lib.load().wc_conv_narrow64_supported(N, H, W, C, w.shape[0], k))
 
 
 def narrow_forward(x, w, bias=None, relu=False, mirrored=False):
@@ -527,11 +571,11 @@ class _NarrowInConv(torch.autograd.Function):
             if _storage_extent(dw) != dw.numel():
                 raise ValueError("weight must be dense")
             db = torch.empty(O, dtype=torch.float32, device=w.device) if ctx.has_bias else None
-            nb = lib.wc_conv_wrw_narrow_workspace_bytes(N, H, W, C, O, k)
+            nb = lib.wc_conv_wrw_narrow64_workspace_bytes(N, H, W, C, O, k)
             ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
             xc = x if x.is_contiguous() else x.contiguous()
-            _lib.check(lib.wc_conv_wrw_narrow_f32(_ptr(xc), _ptr(g), N, H, W, C, O, k, _ptr(dw), dw.stride(1), dw.stride(0), dw.stride(2),
-                                                  dw.stride(3), _ptr(db), _ptr(ws), nb, _stream()), "wc_conv_wrw_narrow_f32")
+            _lib.check(lib.wc_conv_wrw_narrow64_f32(_ptr(xc), _ptr(g), N, H, W, C, O, k, _ptr(dw), dw.stride(1), dw.stride(0), dw.stride(2),
+                                                    dw.stride(3), _ptr(db), _ptr(ws), nb, _stream()), "wc_conv_wrw_narrow64_f32")
         return dx, dw, db
 
 

@@ -19,9 +19,12 @@
 //     iteration = (tap, 32 input channels) = 2 k-steps; two LDS stages, one barrier per iteration, hand-placed: fragments
 //     of k-step 0 right behind the barrier, then the MFMAs with the next iteration's addresses, DMAs and the fragment
 //     reads of k-step 1 in their shadow.
+//     NB = 1 (128 pixels x 64 outputs) is the tile of a width that is 64 beyond a multiple of 128 (the DC critic's 64-filter layers).
 //   * small grids (< ~100 workgroups) share the (tap, chunk) loop over blockIdx.z (conv_ksplit_reduce_kernel finishes).
 //   * weight gradient: conv_wrw_kernel (pixel-major tiles, ds_read_b64_tr_b16 fragments, split over pixel ranges) +
-//     conv_wrw_reduce_kernel (fixed-order sum into the weight's layout, 4x4 slices folded back onto 3x3 taps).
+//     conv_wrw_reduce_kernel (fixed-order sum into the weight's layout, 4x4 slices folded back onto 3x3 taps); 256 x 256, 128 x 128 or
+//     -- a 64-channel side -- 64 x 64 tiles.
+//   * conv(relu(x)) and conv(leaky_relu(x)) apply the activation while x is split (conv_split_*_kernel, split_act).
 // MFMA-bound by design: 3 * 2*M*Cout*K flop on the fp16 pipe against 2*M*Cout*K on the fp32 pipe (157 TFLOP/s peak).
 #include "wc_common.h"
 #include "../../include/wc_hip.h"
@@ -260,19 +263,34 @@ __global__ __launch_bounds__(256) void conv_ksplit_reduce_kernel(const float* __
     }
 }
 
+// the activation in front of a split: relu 0 = none, 1 = ReLU, 2 = LeakyReLU (x > 0 ? x : slope * x, one fp32 multiply; Keras's
+// LeakyReLU of the DC critic, discriminator.py:59-60)
+__device__ __forceinline__ f32x4 split_act(f32x4 v, int relu, float slope)
+{
+    if (relu == 1) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+    else if (relu == 2) {
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = v[j] > 0.f ? v[j] : slope * v[j];
+    }
+    return v;
+}
+
 // ---- max |x|: one partial per workgroup (no atomics: deterministic, nothing to clear); the consumers fold the partials ---
 constexpr int kAmaxBlocks = 512;
 
 __global__ __launch_bounds__(256) void conv_absmax_kernel(const float* __restrict__ x, int64_t n4, int64_t n, float* __restrict__ partial,
-                                                          float* __restrict__ colsum = nullptr, int c4n = 0)
+                                                          float* __restrict__ colsum = nullptr, int c4n = 0, float leaky = -1.f)
 {
+    // leaky >= 0: the maximum of LeakyReLU(x) with that slope (the planes of the leaky split are those of the activated tensor: the same
+    // scale as measuring leaky_relu(x) itself); the column sums stay those of x as given
     __shared__ float red[4];
     __shared__ f32x4 red4[256];
     float m = 0.f;
     f32x4 cs = {0.f, 0.f, 0.f, 0.f};
     for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * i);
-        m = fmaxf(fmaxf(m, fabsf(v[0])), fmaxf(fabsf(v[1]), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+        const f32x4 u = leaky >= 0.f ? split_act(v, 2, leaky) : v;
+        m = fmaxf(fmaxf(m, fabsf(u[0])), fmaxf(fabsf(u[1]), fmaxf(fabsf(u[2]), fabsf(u[3]))));
         cs += v;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) for (int64_t i = 4 * n4; i < n; ++i) m = fmaxf(m, fabsf(x[i]));
@@ -306,16 +324,28 @@ __device__ __forceinline__ float scale_of(const float* __restrict__ partial, flo
     return ldexpf(1.0f, 14 - e);
 }
 
+// the backward of that LeakyReLU on the data gradient, in place: dx *= (x > 0 ? 1 : slope)
+__global__ __launch_bounds__(256) void conv_leaky_bwd_kernel(float* __restrict__ dx, const float* __restrict__ x, int64_t n4, float slope)
+{
+    for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        f32x4 g = *reinterpret_cast<const f32x4*>(dx + 4 * i);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * i);
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) g[j] = v[j] > 0.f ? g[j] : slope * g[j];
+        *reinterpret_cast<f32x4*>(dx + 4 * i) = g;
+    }
+}
+
 // ---- activation split: hi = fp16(x*s), lo = fp16(x*s - hi), optional ReLU first ------------------------------------
 __global__ __launch_bounds__(256) void conv_split_kernel(const float* __restrict__ x, int64_t n4, const float* __restrict__ amax,
                                                          int relu, _Float16* __restrict__ hi, _Float16* __restrict__ lo,
-                                                         float* __restrict__ scale_out)
+                                                         float* __restrict__ scale_out, float slope = 0.f)
 {
     const float s = scale_of(amax);
     if (blockIdx.x == 0 && threadIdx.x == 0) scale_out[0] = s;
     for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * i);
-        if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+        v = split_act(v, relu, slope);
         v = v * s;
         f16x4 h, l;
         #pragma unroll
@@ -379,7 +409,8 @@ __global__ __launch_bounds__(kAmaxBlocks) void conv_hist_seed_kernel(float* __re
 
 __global__ __launch_bounds__(256) void conv_split_hist_kernel(const float* __restrict__ x, int64_t n4, int relu, _Float16* __restrict__ hi,
                                                               _Float16* __restrict__ lo, float* __restrict__ scale_out,
-                                                              float* __restrict__ hist, float* __restrict__ colsum, int c4n)
+                                                              float* __restrict__ hist, float* __restrict__ colsum, int c4n,
+                                                              float slope = 0.f)
 {
     __shared__ float red[4];
     __shared__ f32x4 red4[256];
@@ -422,7 +453,7 @@ __global__ __launch_bounds__(256) void conv_split_hist_kernel(const float* __res
     for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * i);
         cs += v;                                   // (the bias gradient's column sums are of the tensor as given, as in conv_absmax_kernel)
-        if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+        v = split_act(v, relu, slope);
         m = fmaxf(fmaxf(m, fabsf(v[0])), fmaxf(fabsf(v[1]), fmaxf(fabsf(v[2]), fabsf(v[3]))));
         v = v * s;
         f16x4 h, l;
@@ -459,7 +490,7 @@ __global__ __launch_bounds__(256) void conv_split_hist_kernel(const float* __res
 constexpr int kHistRedoWord = 2 * kHistArray;
 __global__ __launch_bounds__(256) void conv_split_redo_kernel(const float* __restrict__ x, int64_t n4, int relu, _Float16* __restrict__ hi,
                                                               _Float16* __restrict__ lo, float* __restrict__ scale_out,
-                                                              float* __restrict__ hist)
+                                                              float* __restrict__ hist, float slope = 0.f)
 {
     typedef int i32x2h __attribute__((ext_vector_type(2)));
     float mx[2] = {0.f, 0.f};
@@ -493,7 +524,7 @@ __global__ __launch_bounds__(256) void conv_split_redo_kernel(const float* __res
     }
     for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * i);
-        if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+        v = split_act(v, relu, slope);
         v = v * s;
         f16x4 h, l;
         #pragma unroll
@@ -621,6 +652,10 @@ __global__ __launch_bounds__(256) void conv_wrw_kernel(WrwArgs a)
     constexpr int TA = 64 * MB, TB = 64 * NB;
     constexpr int A_BYTES = 2 * MB * 4 * 1024, B_BYTES = 2 * NB * 4 * 1024, STAGE = A_BYTES + B_BYTES;
     constexpr int AQ = (2 * MB) / 4, BQ = (2 * NB) / 4;
+    // <1, 1> (a 64 x 64 tile, for layers with a 64-channel side): two 32-channel blocks per operand and four waves, so a wave stages ONE
+    // block of ONE operand (waves 0, 1: the rows' blocks, waves 2, 3: the columns') instead of AQ blocks of each
+    constexpr bool ONE = MB == 1 && NB == 1;
+    static_assert(ONE || (MB >= 2 && NB >= 2), "a wave stages whole blocks of both operands, or one block of one");
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -683,8 +718,8 @@ __global__ __launch_bounds__(256) void conv_wrw_kernel(WrwArgs a)
 
     // the hand-placed iteration of conv_f16x3_kernel: fragments of k-step 0 behind the barrier, the next chunk's
     // addresses and DMAs and the transposing reads of k-step 1 in the shadow of the MFMAs
-    constexpr int NA = AQ * 4, ND = NA + BQ * 4, HALF = ND / 2, PER = 3 * MB * NB, GAP = PER / HALF;
-    static_assert(PER % HALF == 0, "DMAs spread evenly");
+    constexpr int NA = ONE ? 4 : AQ * 4, ND = ONE ? 4 : NA + BQ * 4, HALF = ND / 2, PER = 3 * MB * NB, GAP = ONE ? 1 : PER / HALF;
+    static_assert(ONE || PER % HALF == 0, "DMAs spread evenly");
     const char* pA[2][2]; const char* pB[2][2];     // [k-step][hi | lo] sources of this lane's first block
     int stA[2], stB[2];                             // bytes to the next 32-channel block (0 on the zero line)
     unsigned sb_next = 0;
@@ -694,6 +729,16 @@ __global__ __launch_bounds__(256) void conv_wrw_kernel(WrwArgs a)
             const unsigned m = c * 32 + s * 16 + (lane >> 2);
             const unsigned n = __umulhi(m, a.magHW) >> a.shHW, rem = m - n * HW;
             const unsigned yy = __umulhi(rem, a.magW) >> a.shW, xx = rem - yy * a.W;
+            if constexpr (ONE) {                    // this wave's operand (wave-uniform) and block: pA carries its sources
+                const bool isb = wave >= 2;
+                const int py = isb ? yy * a.B.stride + dyb : yy * a.A.stride + dya, px = isb ? xx * a.B.stride + dxb : xx * a.A.stride + dxa;
+                const int Hp = isb ? a.B.Hp : a.A.Hp, Wp = isb ? a.B.Wp : a.A.Wp, Cc = isb ? a.B.C : a.A.C;
+                const bool okp = (unsigned)py < (unsigned)Hp && (unsigned)px < (unsigned)Wp;
+                const int64_t ep = ((int64_t)((n * Hp + py) * Wp + px)) * Cc + (isb ? tb * TB : ta * TA) + (wave & 1) * 32 + c8;
+                pA[s][0] = reinterpret_cast<const char*>(okp ? (isb ? a.B.hi : a.A.hi) + ep : a.zero + c8);
+                pA[s][1] = reinterpret_cast<const char*>(okp ? (isb ? a.B.lo : a.A.lo) + ep : a.zero + c8);
+                continue;
+            }
             const int ay = yy * a.A.stride + dya, ax = xx * a.A.stride + dxa;
             const int by = yy * a.B.stride + dyb, bx = xx * a.B.stride + dxb;
             const bool oka = (unsigned)ay < (unsigned)a.A.Hp && (unsigned)ax < (unsigned)a.A.Wp;
@@ -709,7 +754,9 @@ __global__ __launch_bounds__(256) void conv_wrw_kernel(WrwArgs a)
         sb_next = __builtin_amdgcn_readfirstlane(lds0 + stage * STAGE);
     };
     auto dma = [&](int d) {
-        if (d < NA) {
+        if constexpr (ONE) {                        // d = (k-step, hi | lo) of the wave's block; A's blocks first, then B's (A_BYTES = 8 KiB)
+            lds_dma16(pA[d >> 1][d & 1], sb_next + (((wave * 2) + (d >> 1)) * 2 + (d & 1)) * 1024);
+        } else if (d < NA) {
             const int s = d / (AQ * 2), q = (d >> 1) % AQ, pl = d & 1;
             lds_dma16(pA[s][pl] + q * stA[s], sb_next + (((wave * AQ + q) * 2 + s) * 2 + pl) * 1024);
         } else {
@@ -753,7 +800,7 @@ __global__ __launch_bounds__(256) void conv_wrw_kernel(WrwArgs a)
             for (int g = 0; g < PER; ++g) {
                 const int prod = g / (MB * NB), i = (g / NB) % MB, j = g % NB;
                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ks][i][prod == 0 ? 1 : 0], fb[ks][j][prod == 1 ? 1 : 0], acc[i][j], 0, 0, 0);
-                if ((g + 1) % GAP == 0) {
+                if ((g + 1) % GAP == 0 && g / GAP < HALF) {     // (<1, 1>: two DMAs behind the first two of three MFMAs)
                     dma(ks * HALF + g / GAP);
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -875,7 +922,8 @@ __global__ __launch_bounds__(512, 1) void conv_wrw_narrow_kernel(NarrowWrwArgs a
     const int64_t p0 = ((int64_t)blockIdx.x * 8 + wave) * a.pix_per_wave;
     int64_t p1 = p0 + a.pix_per_wave;
     if (p1 > a.M) p1 = a.M;
-    const float* gyc = a.gy + grp * 128 + 4 * i;
+    // (Cout % 128 == 64: the last group's upper half has no channels -- those lanes read the group's first ones, nobody reads their results)
+    const float* gyc = a.gy + grp * 128 + (grp * 128 + 4 * i < a.Cout ? 4 * i : 0);
     constexpr int U = 8;
     for (int64_t p = p0; p < p1; p += 2 * U) {
         float av[U]; f32x4 bv[U];
@@ -917,7 +965,7 @@ __global__ __launch_bounds__(512, 1) void conv_wrw_narrow_kernel(NarrowWrwArgs a
 // A workgroup = 32 elements x 8 groups of partials (every 8th partial each, 16 loads in flight), folded through LDS in a fixed order.
 __global__ __launch_bounds__(256) void conv_wrw_narrow_reduce_kernel(const float* __restrict__ partial, int nparts, int Cin, int ks, int nrow,
                                                                      float* __restrict__ dw, int64_t sk, int64_t sn, int64_t sr, int64_t ss,
-                                                                     float* __restrict__ db)
+                                                                     float* __restrict__ db, int Cout)
 {
     __shared__ float red[8][32];
     const int el = threadIdx.x & 31, pg = threadIdx.x >> 5;
@@ -941,6 +989,7 @@ __global__ __launch_bounds__(256) void conv_wrw_narrow_reduce_kernel(const float
     const int q = e >> 10, r = (e >> 6) & 15, ln = e & 63;
     const int row = (r & 3) + 8 * (r >> 2) + 4 * (ln >> 5);
     const int o = blockIdx.y * 128 + 4 * (ln & 31) + q;
+    if (o >= Cout) return;
     if (row < nrow) {
         const int tap = row / Cin, c = row - tap * Cin;
         dw[c * sk + o * sn + (tap / ks) * sr + (tap % ks) * ss] = sum;
@@ -1092,6 +1141,43 @@ hipError_t launch_conv(const ConvArgs& a, hipStream_t st)
 
 extern "C" {
 
+static int split_measured(const float* x, int64_t n, int relu, float slope, void* hi, void* lo, float* scale, void* amax_scratch,
+                          float* colsum_partials, int C, hipStream_t st)
+{
+    if (!x || !hi || !lo || !scale || !amax_scratch || n <= 0 || (n & 3)) return WC_ERR_ARG;
+    if (colsum_partials && (C <= 0 || (C & 3) || 256 % (C >> 2) != 0 || n % C != 0)) return WC_ERR_SHAPE;
+    hipLaunchKernelGGL(conv_absmax_kernel, dim3(kAmaxBlocks), dim3(256), 0, st, x, n / 4, n, (float*)amax_scratch,
+                       colsum_partials, colsum_partials ? C >> 2 : 0, relu == 2 ? slope : -1.f);
+    hipLaunchKernelGGL(conv_split_kernel, dim3(grid_for(n / 4)), dim3(256), 0, st, x, n / 4, (const float*)amax_scratch, relu,
+                       (_Float16*)hi, (_Float16*)lo, scale, slope);
+    return (int)hipGetLastError();
+}
+
+static int split_hist(const float* x, int64_t n, int relu, float slope, void* hi, void* lo, float* scale, float* colsum_partials, int C,
+                      float* hist, int bootstrap, hipStream_t st)
+{
+    if (!x || !hi || !lo || !scale || !hist || n <= 0 || (n & 3)) return WC_ERR_ARG;
+    if (colsum_partials && (C <= 0 || (C & 3) || 256 % (C >> 2) != 0 || n % C != 0)) return WC_ERR_SHAPE;
+    if (bootstrap & 1) {   // the site's first call: the measured maximum (the two-launch form, bit for bit), left in the record
+        hipLaunchKernelGGL(conv_absmax_kernel, dim3(kAmaxBlocks), dim3(256), 0, st, x, n / 4, n, hist, colsum_partials, colsum_partials ? C >> 2 : 0,
+                           relu == 2 ? slope : -1.f);
+        hipLaunchKernelGGL(conv_split_kernel, dim3(grid_for(n / 4)), dim3(256), 0, st, x, n / 4, (const float*)hist, relu, (_Float16*)hi,
+                           (_Float16*)lo, scale, slope);
+        hipLaunchKernelGGL(conv_hist_seed_kernel, dim3(1), dim3(kAmaxBlocks), 0, st, hist);
+        return (int)hipGetLastError();
+    }
+    // always kAmaxBlocks workgroups: they are the partial rows conv_wrw_reduce_kernel adds up
+    hipLaunchKernelGGL(conv_split_hist_kernel, dim3(kAmaxBlocks), dim3(256), 0, st, x, n / 4, relu, (_Float16*)hi, (_Float16*)lo, scale,
+                       hist, colsum_partials, colsum_partials ? C >> 2 : 0, slope);
+    if (!(bootstrap & 2)) {
+        // (a small grid: inside the window -- the usual case -- the launch is 64 workgroups reading 8 KB each and returning; outside it they
+        // stride over the tensor)
+        const unsigned g2 = grid_for(n / 4) < 64u ? grid_for(n / 4) : 64u;
+        hipLaunchKernelGGL(conv_split_redo_kernel, dim3(g2), dim3(256), 0, st, x, n / 4, relu, (_Float16*)hi, (_Float16*)lo, scale, hist, slope);
+    }
+    return (int)hipGetLastError();
+}
+
 int wc_conv_split_f32(const float* x, int64_t n, int relu, void* hi, void* lo, float* scale, void* amax_scratch, wc_stream_t stream)
 {
     return wc_conv_split_colsum_f32(x, n, relu, hi, lo, scale, amax_scratch, nullptr, 0, stream);
@@ -1100,38 +1186,34 @@ int wc_conv_split_f32(const float* x, int64_t n, int relu, void* hi, void* lo, f
 int wc_conv_split_colsum_f32(const float* x, int64_t n, int relu, void* hi, void* lo, float* scale, void* amax_scratch,
                              float* colsum_partials, int C, wc_stream_t stream)
 {
-    hipStream_t st = (hipStream_t)stream;
-    if (!x || !hi || !lo || !scale || !amax_scratch || n <= 0 || (n & 3)) return WC_ERR_ARG;
-    if (colsum_partials && (C <= 0 || (C & 3) || 256 % (C >> 2) != 0 || n % C != 0)) return WC_ERR_SHAPE;
-    hipLaunchKernelGGL(conv_absmax_kernel, dim3(kAmaxBlocks), dim3(256), 0, st, x, n / 4, n, (float*)amax_scratch,
-                       colsum_partials, colsum_partials ? C >> 2 : 0);
-    hipLaunchKernelGGL(conv_split_kernel, dim3(grid_for(n / 4)), dim3(256), 0, st, x, n / 4, (const float*)amax_scratch, relu,
-                       (_Float16*)hi, (_Float16*)lo, scale);
-    return (int)hipGetLastError();
+    return split_measured(x, n, relu ? 1 : 0, 0.f, hi, lo, scale, amax_scratch, colsum_partials, C, (hipStream_t)stream);
 }
 
 int wc_conv_split_hist_f32(const float* x, int64_t n, int relu, void* hi, void* lo, float* scale, float* colsum_partials, int C,
                            float* hist, int bootstrap, wc_stream_t stream)
 {
-    hipStream_t st = (hipStream_t)stream;
-    if (!x || !hi || !lo || !scale || !hist || n <= 0 || (n & 3)) return WC_ERR_ARG;
-    if (colsum_partials && (C <= 0 || (C & 3) || 256 % (C >> 2) != 0 || n % C != 0)) return WC_ERR_SHAPE;
-    if (bootstrap & 1) {   // the site's first call: the measured maximum (the two-launch form, bit for bit), left in the record
-        hipLaunchKernelGGL(conv_absmax_kernel, dim3(kAmaxBlocks), dim3(256), 0, st, x, n / 4, n, hist, colsum_partials, colsum_partials ? C >> 2 : 0);
-        hipLaunchKernelGGL(conv_split_kernel, dim3(grid_for(n / 4)), dim3(256), 0, st, x, n / 4, (const float*)hist, relu, (_Float16*)hi,
-                           (_Float16*)lo, scale);
-        hipLaunchKernelGGL(conv_hist_seed_kernel, dim3(1), dim3(kAmaxBlocks), 0, st, hist);
-        return (int)hipGetLastError();
-    }
-    // always kAmaxBlocks workgroups: they are the partial rows conv_wrw_reduce_kernel adds up
-    hipLaunchKernelGGL(conv_split_hist_kernel, dim3(kAmaxBlocks), dim3(256), 0, st, x, n / 4, relu, (_Float16*)hi, (_Float16*)lo, scale,
-                       hist, colsum_partials, colsum_partials ? C >> 2 : 0);
-    if (!(bootstrap & 2)) {
-        // (a small grid: inside the window -- the usual case -- the launch is 64 workgroups reading 8 KB each and returning; outside it they
-        // stride over the tensor)
-        const unsigned g2 = grid_for(n / 4) < 64u ? grid_for(n / 4) : 64u;
-        hipLaunchKernelGGL(conv_split_redo_kernel, dim3(g2), dim3(256), 0, st, x, n / 4, relu, (_Float16*)hi, (_Float16*)lo, scale, hist);
-    }
+    return split_hist(x, n, relu ? 1 : 0, 0.f, hi, lo, scale, colsum_partials, C, hist, bootstrap, (hipStream_t)stream);
+}
+
+// LeakyReLU in front of the split.  Slope 0 IS the ReLU: it takes the ReLU form (fmaxf: the same plane bits as relu = 1).
+int wc_conv_split_leaky_f32(const float* x, int64_t n, float negative_slope, void* hi, void* lo, float* scale, void* amax_scratch,
+                            float* colsum_partials, int C, wc_stream_t stream)
+{
+    if (!(negative_slope >= 0.f && negative_slope <= 1.f)) return WC_ERR_ARG;     // (the activation must not grow the tensor: the history's window is sized for |x|)
+    return split_measured(x, n, negative_slope == 0.f ? 1 : 2, negative_slope, hi, lo, scale, amax_scratch, colsum_partials, C, (hipStream_t)stream);
+}
+
+int wc_conv_split_hist_leaky_f32(const float* x, int64_t n, float negative_slope, void* hi, void* lo, float* scale, float* colsum_partials, int C,
+                                 float* hist, int bootstrap, wc_stream_t stream)
+{
+    if (!(negative_slope >= 0.f && negative_slope <= 1.f)) return WC_ERR_ARG;
+    return split_hist(x, n, negative_slope == 0.f ? 1 : 2, negative_slope, hi, lo, scale, colsum_partials, C, hist, bootstrap, (hipStream_t)stream);
+}
+
+int wc_conv_leaky_bwd_f32(float* dx, const float* x, int64_t n, float negative_slope, wc_stream_t stream)
+{
+    if (!dx || !x || n <= 0 || (n & 3)) return WC_ERR_ARG;
+    hipLaunchKernelGGL(conv_leaky_bwd_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, dx, x, n / 4, negative_slope);
     return (int)hipGetLastError();
 }
 
@@ -1209,7 +1291,7 @@ int wc_conv_supported(const wc_conv_geom* g)
 {
     if (!g) return 0;
     if (g->ntaps < 1 || g->ntaps > kMaxTaps || g->nphase < 1 || g->nphase > kMaxPhase) return 0;
-    if ((g->Cin & 31) || (g->Cout & 127)) return 0;
+    if ((g->Cin & 31) || (g->Cout & 63)) return 0;    // (Cout % 128 == 64: the 64-output tile <2, 1>)
     const int64_t M = (int64_t)g->N * g->H * g->W;
     if (M <= 0 || (M & 127) || M > (int64_t)1 << 31) return 0;
     if ((int64_t)g->N * g->Hin * g->Win > (int64_t)1 << 31) return 0;
@@ -1226,7 +1308,7 @@ static int conv_ksplit(const wc_conv_geom* g)
     // small grids leave most CUs idle with 128-point x (128|256)-output tiles: share the (tap, chunk) loop
     const int64_t M = (int64_t)g->N * g->H * g->W;
     const bool wide = (g->Cout % 256) == 0;
-    const int64_t wgs = (M / 128) * g->nphase * (g->Cout / (wide ? 256 : 128));
+    const int64_t wgs = (M / 128) * g->nphase * (g->Cout / (wide ? 256 : (g->Cout % 128) ? 64 : 128));
     const int iters = g->ntaps * (g->Cin / 32);
     if (wgs > kKsplitMaxWgs || iters < 8) return 1;
     int k = (int)((kKsplitTargetWgs + wgs - 1) / wgs);
@@ -1267,7 +1349,8 @@ int wc_conv_f16x3(const void* xhi, const void* xlo, const float* xscale, const v
     // the larger pixel tile when it still gives every CU a workgroup
     const int64_t wgs_big = (M / 256) * g->nphase * (g->Cout / (wide ? 256 : 128));
     hipError_t e;
-    if (a.ksplit == 1 && (M % 256) == 0 && wgs_big >= 256) e = wide ? launch_conv<4, 4>(a, st) : launch_conv<4, 2>(a, st);
+    if (g->Cout % 128)                                      e = a.ksplit > 1 ? launch_conv<2, 1, true>(a, st) : launch_conv<2, 1>(a, st);
+    else if (a.ksplit == 1 && (M % 256) == 0 && wgs_big >= 256) e = wide ? launch_conv<4, 4>(a, st) : launch_conv<4, 2>(a, st);
     else if (a.ksplit > 1)                                  e = wide ? launch_conv<2, 4, true>(a, st) : launch_conv<2, 2, true>(a, st);
     else                                                    e = wide ? launch_conv<2, 4>(a, st) : launch_conv<2, 2>(a, st);
     if (e != hipSuccess) return (int)e;
@@ -1283,7 +1366,7 @@ static int wrw_splits(const wc_conv_geom* g, int* tile)
 {
     // 256 x 256 tiles when there are enough of them (a 1x1 convolution has one slice: 128 x 128 tiles then)
     const bool wide = (g->Cin % 256 == 0) && (g->Cout % 256 == 0) && g->nphase * g->ntaps * (g->Cin / 256) * (g->Cout / 256) >= 4;
-    *tile = wide ? 256 : 128;
+    *tile = wide ? 256 : ((g->Cin % 128) || (g->Cout % 128)) ? 64 : 128;     // (a 64-channel side: 64 x 64 tiles)
     const int tiles = g->nphase * g->ntaps * (g->Cin / *tile) * (g->Cout / *tile);
     const int64_t nchunks = (int64_t)g->N * g->H * g->W / 32;
     // The workgroups of one pixel range (one per slice and tile) read the same activations: a split count that is a
@@ -1297,12 +1380,13 @@ static int wrw_splits(const wc_conv_geom* g, int* tile)
 }
 
 int wc_conv_wrw_narrow_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize);
+int wc_conv_narrow64_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize);
 
 int wc_conv_fwd_narrow_f32(const float* x, const float* w, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
                            const float* bias, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize, int relu, float* y, wc_stream_t stream)
 {
     if (!x || !w || !y) return WC_ERR_ARG;
-    if (!wc_conv_wrw_narrow_supported(N, H, W, Cin, Cout, ksize) || N * H * W * Cin >= ((int64_t)1 << 31)) return WC_ERR_SHAPE;
+    if (!wc_conv_narrow64_supported(N, H, W, Cin, Cout, ksize) || N * H * W * Cin >= ((int64_t)1 << 31)) return WC_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     NarrowFwdArgs a = {};
     a.x = x; a.w = w; a.bias = bias; a.y = y;
@@ -1339,27 +1423,38 @@ static int64_t narrow_wrw_parts(int64_t M, int64_t* pix_per_wave)
     return (M + 8 * ppw - 1) / (8 * ppw);
 }
 
-int wc_conv_wrw_narrow_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize)
+int wc_conv_narrow64_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize)
 {
     if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3)) return 0;
-    if (ksize * ksize * Cin >= 32 || (Cout & 127)) return 0;
+    if (ksize * ksize * Cin >= 32 || (Cout & 63)) return 0;
     return N * H * W < ((int64_t)1 << 31) ? 1 : 0;
+}
+
+// (the ABI 7 predicate: multiples of 128 only; wc_conv_narrow64_supported is the whole set)
+int wc_conv_wrw_narrow_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize)
+{
+    return ((Cout & 127) == 0 && wc_conv_narrow64_supported(N, H, W, Cin, Cout, ksize)) ? 1 : 0;
+}
+
+size_t wc_conv_wrw_narrow64_workspace_bytes(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize)
+{
+    if (!wc_conv_narrow64_supported(N, H, W, Cin, Cout, ksize)) return 0;
+    int64_t ppw;
+    return (size_t)narrow_wrw_parts(N * H * W, &ppw) * ((Cout + 127) / 128) * 4096 * sizeof(float);
 }
 
 size_t wc_conv_wrw_narrow_workspace_bytes(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize)
 {
-    if (!wc_conv_wrw_narrow_supported(N, H, W, Cin, Cout, ksize)) return 0;
-    int64_t ppw;
-    return (size_t)narrow_wrw_parts(N * H * W, &ppw) * (Cout / 128) * 4096 * sizeof(float);
+    return wc_conv_wrw_narrow_supported(N, H, W, Cin, Cout, ksize) ? wc_conv_wrw_narrow64_workspace_bytes(N, H, W, Cin, Cout, ksize) : 0;
 }
 
-int wc_conv_wrw_narrow_f32(const float* x, const float* gy, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize,
-                           float* dw, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s, float* db,
-                           void* ws, size_t ws_bytes, wc_stream_t stream)
+int wc_conv_wrw_narrow64_f32(const float* x, const float* gy, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize,
+                             float* dw, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s, float* db,
+                             void* ws, size_t ws_bytes, wc_stream_t stream)
 {
     if (!x || !gy || !dw || !ws) return WC_ERR_ARG;
-    if (!wc_conv_wrw_narrow_supported(N, H, W, Cin, Cout, ksize)) return WC_ERR_SHAPE;
-    if (ws_bytes < wc_conv_wrw_narrow_workspace_bytes(N, H, W, Cin, Cout, ksize)) return WC_ERR_WORKSPACE;
+    if (!wc_conv_narrow64_supported(N, H, W, Cin, Cout, ksize)) return WC_ERR_SHAPE;
+    if (ws_bytes < wc_conv_wrw_narrow64_workspace_bytes(N, H, W, Cin, Cout, ksize)) return WC_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     NarrowWrwArgs a = {};
     a.x = x; a.gy = gy; a.partial = (float*)ws;
@@ -1368,13 +1463,23 @@ int wc_conv_wrw_narrow_f32(const float* x, const float* gy, int64_t N, int64_t H
     magic_u31((unsigned)W, &a.magW, &a.shW);
     a.M = N * H * W;
     const int nparts = (int)narrow_wrw_parts(a.M, &a.pix_per_wave);
+    const int ngrp = (Cout + 127) / 128;
     constexpr int lds = 8 * 4096 * 4;
     hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(conv_wrw_narrow_kernel), lds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(conv_wrw_narrow_kernel, dim3(nparts, Cout / 128), dim3(512), lds, st, a);
-    hipLaunchKernelGGL(conv_wrw_narrow_reduce_kernel, dim3(128, Cout / 128), dim3(256), 0, st, (const float*)ws, nparts, Cin, ksize, a.nrow,
-                       dw, stride_k, stride_n, stride_r, stride_s, db);
+    hipLaunchKernelGGL(conv_wrw_narrow_kernel, dim3(nparts, ngrp), dim3(512), lds, st, a);
+    hipLaunchKernelGGL(conv_wrw_narrow_reduce_kernel, dim3(128, ngrp), dim3(256), 0, st, (const float*)ws, nparts, Cin, ksize, a.nrow,
+                       dw, stride_k, stride_n, stride_r, stride_s, db, Cout);
     return (int)hipGetLastError();
+}
+
+int wc_conv_wrw_narrow_f32(const float* x, const float* gy, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize,
+                           float* dw, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s, float* db,
+                           void* ws, size_t ws_bytes, wc_stream_t stream)
+{
+    if (!x || !gy || !dw || !ws) return WC_ERR_ARG;
+    if (!wc_conv_wrw_narrow_supported(N, H, W, Cin, Cout, ksize)) return WC_ERR_SHAPE;
+    return wc_conv_wrw_narrow64_f32(x, gy, N, H, W, Cin, Cout, ksize, dw, stride_k, stride_n, stride_r, stride_s, db, ws, ws_bytes, stream);
 }
 
 size_t wc_conv_wrw_workspace_bytes(const wc_conv_geom* g)
@@ -1399,7 +1504,7 @@ int wc_conv_wrw_bias_f16x3(const void* xhi, const void* xlo, const float* xscale
 {
     hipStream_t st = (hipStream_t)stream;
     if (!xhi || !xlo || !xscale || !ghi || !glo || !gscale || !zero_line || !g || !dw || !ws) return WC_ERR_NULL;
-    if (!wc_conv_supported(g) || (g->Cin & 127) || g->W < 2 || g->H * g->W < 2) return WC_ERR_SHAPE;
+    if (!wc_conv_supported(g) || (g->Cin & 63) || g->W < 2 || g->H * g->W < 2) return WC_ERR_SHAPE;
     if (ws_bytes < wc_conv_wrw_workspace_bytes(g)) return WC_ERR_WORKSPACE;
     int T;
     int splits = wrw_splits(g, &T);
@@ -1446,6 +1551,11 @@ int wc_conv_wrw_bias_f16x3(const void* xhi, const void* xlo, const float* xscale
         e = wc_set_max_lds(reinterpret_cast<const void*>(conv_wrw_kernel<4, 4>), LDS);
         if (e != hipSuccess) return (int)e;
         hipLaunchKernelGGL((conv_wrw_kernel<4, 4>), grid, dim3(256), LDS, st, a);
+    } else if (T == 64) {
+        constexpr int LDS = 2 * (2 * 1 * 4 * 1024 + 2 * 1 * 4 * 1024);
+        e = wc_set_max_lds(reinterpret_cast<const void*>(conv_wrw_kernel<1, 1>), LDS);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL((conv_wrw_kernel<1, 1>), grid, dim3(256), LDS, st, a);
     } else {
         constexpr int LDS = 2 * (2 * 2 * 4 * 1024 + 2 * 2 * 4 * 1024);
         e = wc_set_max_lds(reinterpret_cast<const void*>(conv_wrw_kernel<2, 2>), LDS);

@@ -5,6 +5,9 @@ defaults to 'n', run.py:298), so it is the stock-torch part of the surrounding s
 on the block convolutions of wc_gan_amd/conv.py (MIOpen for the 3-channel first layers) with the fused spectral-norm op
 (wc_gan_amd/spectral.py) standing in for gan.SNConv2D /
 SNDense / SNEmbeding (discriminator.py:26-33).  Three heads as in discriminator.py:73-85.
+
+arch='dcgan' (scripts/*_dcgan_sn_uncond.sh): DCBlockDown -- LeakyReLU -> Conv2D, 3x3 'same' or 4x4 stride 2 -- and the flatten tail of
+discriminator.py:57-85.
 """
 from __future__ import annotations
 
@@ -55,26 +58,65 @@ class ResBlockDown(nn.Module):
         return h + s
 
 
+LEAKY_SLOPE = 0.3       # Keras's LeakyReLU() default (discriminator.py:59); gradient at x <= 0: slope * g (torch's convention)
+
+
+class DCBlockDown(nn.Module):
+    """The DC critic's block, pre-activation (`dcblock` takes `is_first` like `resblock`, and discriminator.py:59-60 applies a LeakyReLU
+    behind the last block): y = conv(x) for the first block, else conv(leaky(norm(x))); SAME = 3x3 stride 1, DOWN = 4x4 stride 2, both
+    Keras 'same'.  The activation and the convolution are one layer call (Conv2D.forward_leaky)."""
+
+    def __init__(self, in_ch, nfilters, resample, name, norm, conv_layer, is_first):
+        super().__init__()
+        assert resample in ('DOWN', 'SAME')
+        self.resample, self.is_first = resample, is_first
+        self.bn = norm(axis=-1, name=name + '.bn', channels=in_ch)
+        if resample == 'DOWN':
+            self.conv = conv_layer(in_ch, nfilters, (4, 4), name=name + '.conv', stride=2)
+        else:
+            self.conv = conv_layer(in_ch, nfilters, (3, 3), name=name + '.conv')
+
+    def forward(self, x, cls):
+        if self.is_first:
+            return self.conv(x)
+        return self.conv.forward_leaky(self.bn(x, cls), LEAKY_SLOPE)
+
+
 class Discriminator(nn.Module):
     def __init__(self, in_ch, block_sizes, resamples, norm_layer, conv_layer, dense, emb, number_of_classes, type,
-                 sum_pool, dropout):
+                 sum_pool, dropout, arch='res', input_hw=None):
         super().__init__()
         blocks = []
         ch = in_ch
+        self.arch = arch
+        block = ResBlockDown if arch == 'res' else DCBlockDown
         for i, (bs, rs) in enumerate(zip(block_sizes, resamples)):
             bs = int(bs)
-            blocks.append(ResBlockDown(ch, bs, rs, 'Discriminator.' + str(i), norm_layer, conv_layer, is_first=(i == 0)))
+            blocks.append(block(ch, bs, rs, 'Discriminator.' + str(i), norm_layer, conv_layer, is_first=(i == 0)))
             ch = bs
         self.blocks = nn.ModuleList(blocks)
         self.sum_pool, self.type = sum_pool, type
         self.dropout = nn.Dropout(dropout) if dropout else None
+        emb_dim = ch
+        if arch == 'dcgan':     # Flatten in NHWC order (discriminator.py:61-62): the heads read every grid point; sum_pool is ignored
+            h, w = (int(v) for v in input_hw)
+            for rs in resamples:
+                if rs == 'DOWN':
+                    if h % 2 or w % 2:
+                        raise ValueError(f"arch='dcgan': a DOWN block halves a {h} x {w} grid")
+                    h, w = h // 2, w // 2
+            if type == 'PROJECTIVE' and h * w != 1:
+                # the reference embeds into block_sizes[-1] dimensions while y is flattened: the product only exists on a 1 x 1 grid
+                raise ValueError(f"arch='dcgan' with type='PROJECTIVE' needs a 1 x 1 final grid (the embedding has block_sizes[-1] = {ch} "
+                                 f"dimensions, the flattened features {h} x {w} x {ch}); no shipped recipe combines them")
+            ch = h * w * ch
         self.out = dense(ch, 1)
         if type == 'AC_GAN':
             # the class head is a plain Dense in the reference even when spectral=True (discriminator.py:74)
             self.cls_out = nn.Linear(ch, number_of_classes)
             nn.init.xavier_uniform_(self.cls_out.weight); nn.init.zeros_(self.cls_out.bias)
         elif type == 'PROJECTIVE':
-            self.emb = emb(number_of_classes, ch)
+            self.emb = emb(number_of_classes, emb_dim)
 
     def forward(self, x, cls=None):
         from .spectral import prepare_spectral
@@ -82,8 +124,11 @@ class Discriminator(nn.Module):
         y = x
         for blk in self.blocks:
             y = blk(y, cls)
-        y = F.relu(y)
-        y = y.sum(dim=(1, 2)) if self.sum_pool else y.mean(dim=(1, 2))
+        if self.arch == 'dcgan':
+            y = F.leaky_relu(y, LEAKY_SLOPE).flatten(1)
+        else:
+            y = F.relu(y)
+            y = y.sum(dim=(1, 2)) if self.sum_pool else y.mean(dim=(1, 2))
         if self.dropout is not None:
             y = self.dropout(y)
         out = self.out(y)
@@ -104,7 +149,7 @@ def make_discriminator(input_image_shape=(32, 32, 3), input_cls_shape=(1,), bloc
     configs do.  `conv_singular=True` (the reference's default here; run.py:270 passes 0) asks for the
     convolution-operator singular value of SNConv2D, which this harness does not build: it warns and uses the
     reshaped-kernel sigma of the SN-GAN paper."""
-    assert arch == 'res', "only the ResNet critic is built for the harness (dcgan critic: out of the WC path)"
+    assert arch in ('res', 'dcgan')
     assert type in [None, 'AC_GAN', 'PROJECTIVE']
     if spectral and conv_singular:
         import warnings
@@ -133,4 +178,4 @@ def make_discriminator(input_image_shape=(32, 32, 3), input_cls_shape=(1,), bloc
 
     norm_layer = create_norm(norm, after_norm, number_of_classes=number_of_classes, filters_emb=filters_emb)
     return Discriminator(int(input_image_shape[-1]), block_sizes, resamples, norm_layer, conv_layer, dense, emb,
-                         number_of_classes, type, sum_pool, dropout)
+                         number_of_classes, type, sum_pool, dropout, arch=arch, input_hw=input_image_shape[:2])

@@ -61,7 +61,8 @@ class _NarrowConv3x3(torch.autograd.Function):
     against 0.16 ms here, measured); the backward keeps MIOpen's kernels, which are the faster ones there."""
 
     @staticmethod
-    def forward(ctx, x, w, b):                      # x (N,H,W,Cin) contiguous NHWC; w (Cout,Cin,3,3); b (Cout,) | None
+    def forward(ctx, x, w, b, sum_bias=False):      # x (N,H,W,Cin) contiguous NHWC; w (Cout,Cin,3,3); b (Cout,) | None
+        ctx.sum_bias = bool(sum_bias)
         N, H, W, C = x.shape
         O = w.shape[0]
         wall = w.flip(2, 3).permute(1, 0, 2, 3).reshape(C, O * 9)        # [c, (o, a, b)] = w[o, c, 2-a, 2-b]
@@ -81,36 +82,46 @@ class _NarrowConv3x3(torch.autograd.Function):
         own = fast_conv_mod.narrow_out_wrw_supported(x, w) and x.is_contiguous()
         own_w = ctx.needs_input_grad[1] and own
         own_x = ctx.needs_input_grad[0] and own
-        gx, gw, gb = torch.ops.aten.convolution_backward(
-            g.permute(0, 3, 1, 2), x.permute(0, 3, 1, 2), w, [w.shape[0]] if ctx.has_bias else None,
-            [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
-            [ctx.needs_input_grad[0] and not own_x, ctx.needs_input_grad[1] and not own_w, ctx.has_bias and ctx.needs_input_grad[2]])
+        want = [ctx.needs_input_grad[0] and not own_x, ctx.needs_input_grad[1] and not own_w, ctx.has_bias and ctx.needs_input_grad[2]]
+        if ctx.sum_bias and not want[0] and not want[1]:
+            # nothing is left for MIOpen but the bias gradient, a handful of column sums of g: no convolution operator for that
+            # (the DC generator asks for it; the ResNet generators keep the reduction -- and the bits -- they have)
+            gx = gw = None
+            gb = g.sum(dim=(0, 1, 2)) if want[2] else None
+        else:
+            gx, gw, gb = torch.ops.aten.convolution_backward(
+                g.permute(0, 3, 1, 2), x.permute(0, 3, 1, 2), w, [w.shape[0]] if ctx.has_bias else None,
+                [1, 1], [1, 1], [1, 1], False, [0, 0], 1, want)
         gx = gx.permute(0, 2, 3, 1) if gx is not None else None
         gc = g.contiguous() if (own_w or own_x) else None
         if own_w:
             gw = fast_conv_mod.narrow_out_weight_gradient(x, gc, w)
         if own_x:       # the data gradient = the narrow-input FORWARD of gy through the mirrored, transposed weight
             gx = fast_conv_mod.narrow_forward(gc, w, None, mirrored=True)
-        return gx, gw, (gb if ctx.has_bias else None)
+        return gx, gw, (gb if ctx.has_bias else None), None
 
 
 class Conv2D(nn.Module):
-    """Keras-style Conv2D on NHWC tensors (padding='same'); glorot-uniform kernel, zero bias."""
+    """Keras-style Conv2D on NHWC tensors (padding='same'); glorot-uniform kernel, zero bias.
+    stride 2 (the DC critic's DOWN blocks): the 4x4 kernel only -- Keras 'same' then pads 1 and 1, torch's padding=1."""
 
     def __init__(self, in_channels, filters, kernel_size=(3, 3), use_bias=True, name=None, spectral=False,
-                 spectral_iterations=1, fully_diff_spectral=False, conv_singular=True):
+                 spectral_iterations=1, fully_diff_spectral=False, conv_singular=True, stride=1):
         super().__init__()
         k = kernel_size if isinstance(kernel_size, int) else kernel_size[0]
+        if stride not in (1, 2) or (stride == 2 and k != 4):
+            raise ValueError(f"Conv2D: stride 2 is built for the 4x4 kernel ('same' = padding 1), not {k}x{k} / {stride}")
+        self.kind = 'same' if stride == 1 else 'down'          # wc_gan_amd.conv's name of the layer
         if spectral:        # SNConv2D (generator.py:105-106, discriminator.py:27-28): the fused HIP op
             from .spectral import SNConv2d
-            self.conv = SNConv2d(in_channels, filters, k, padding=k // 2, bias=use_bias,
+            self.conv = SNConv2d(in_channels, filters, k, stride=stride, padding=k // 2 if stride == 1 else 1, bias=use_bias,
                                  spectral_iterations=spectral_iterations, fully_diff_spectral=fully_diff_spectral,
                                  conv_singular=conv_singular)
             with torch.no_grad():
                 nn.init.xavier_uniform_(self.conv.weight)
                 self.conv._sn_init(spectral_iterations, fully_diff_spectral, conv_singular)     # u, v for the new kernel
         else:
-            self.conv = nn.Conv2d(in_channels, filters, k, padding=k // 2, bias=use_bias)
+            self.conv = nn.Conv2d(in_channels, filters, k, stride=stride, padding=k // 2 if stride == 1 else 1, bias=use_bias)
             nn.init.xavier_uniform_(self.conv.weight)
         if use_bias:
             nn.init.zeros_(self.conv.bias)
@@ -147,6 +158,16 @@ class Conv2D(nn.Module):
                 return y
         return self.forward(F.relu(x), _w=w)
 
+    def forward_leaky(self, x, negative_slope):
+        """conv(leaky_relu(x)): on the fast path the activation happens while the input is split, as forward_relu's ReLU does, and its
+        backward is one launch over the data gradient (conv.leaky_backward_)"""
+        w = self._weight()
+        if FAST_CONV and x.is_cuda:
+            y = fast_conv_mod.fast_conv_or_none(x, w, self.conv.bias, self.kind, leaky_input=negative_slope, site=self)
+            if y is not None:
+                return y
+        return self.forward(F.leaky_relu(x, negative_slope), _w=w)
+
     def forward(self, x, _w=None):
         c = self.conv
         st = split_of(x)
@@ -154,14 +175,14 @@ class Conv2D(nn.Module):
             return fast_conv_mod.split_conv(x, st, self._weight() if _w is None else _w, c.bias, site=self)
         if (c.out_channels <= 4 and tuple(c.kernel_size) == (3, 3) and not hasattr(c, 'normalized_weight')
                 and x.is_cuda and x.is_contiguous()):
-            return _NarrowConv3x3.apply(x, c.weight, c.bias)
+            return _NarrowConv3x3.apply(x, c.weight, c.bias, getattr(self, 'sum_bias_grad', False))
         # the weight ONCE per forward: a spectrally normalised layer advances its power iteration in normalized_weight()
         w = self._weight() if _w is None else _w
         if FAST_CONV and x.is_cuda:
-            y = fast_conv_mod.fast_conv_or_none(x, w, c.bias, 'same', site=self)      # split-fp16 MFMA implicit GEMM (csrc/wc_conv.hip)
+            y = fast_conv_mod.fast_conv_or_none(x, w, c.bias, self.kind, site=self)      # split-fp16 MFMA implicit GEMM (csrc/wc_conv.hip)
             if y is not None:
                 return y
-        if x.is_cuda and fast_conv_mod.narrow_wrw_supported(x, w):
+        if x.is_cuda and self.kind == 'same' and fast_conv_mod.narrow_wrw_supported(x, w):
             return fast_conv_mod.narrow_in_conv(x, w, c.bias)       # an image-like input: forward and weight / bias gradient on the fp32 matrix pipe (csrc/wc_conv.hip)
         return to_nhwc(c._conv_forward(to_nchw_view(x), w, c.bias))
 
@@ -222,7 +243,7 @@ class _BatchNormNoAffine(nn.Module):
 
     def forward(self, x):
         if self.bn is None:
-            self.bn = nn.BatchNorm2d(x.shape[-1], eps=1e-3, momentum=0.01, affine=False).to(x.device)
+            self.bn = nn.BatchNorm2d(x.shape[-1], eps=1e-3, momentum=0.01, affine=False).to(device=x.device, dtype=x.dtype)
         return to_nhwc(self.bn(to_nchw_view(x)))
 
 
@@ -402,15 +423,34 @@ class ResBlockUp(nn.Module):
 
 
 class DCBlockUp(nn.Module):
+    """The DC generator's block, pre-activation like the ResNet block (`dcblock` takes `is_first` as `resblock`
+    does, and generator.py:154-155 applies Generator.BN.Final + ReLU behind the LAST block): y = deconv4x4_s2_same(relu(norm(x))), with a
+    bias and no spectral norm (generator.py:148).  UP: on the 4x4 stride-2 transposed kernel of wc_gan_amd.conv ('up'), the site's
+    planes handed over where K3 writes them; SAME (no recipe): a 4x4 stride-1 transposed convolution on torch."""
+
     def __init__(self, in_ch, nfilters, resample, name, norm):
         super().__init__()
+        assert resample in ('UP', 'SAME')
+        self.resample = resample
         self.deconv = nn.ConvTranspose2d(in_ch, nfilters, 4, stride=2 if resample == 'UP' else 1,
                                          padding=1 if resample == 'UP' else 0).to(memory_format=torch.channels_last)
-        self.bn = norm(axis=-1, name=name + '.bn', channels=nfilters)
+        self.bn = norm(axis=-1, name=name + '.bn', channels=in_ch)
+
+    def takes_planes(self, shape, kind='up'):
+        """Will forward() read an input of this shape as planes handed over by the WC site in front of the deconvolution?"""
+        w = self.deconv.weight
+        return (FAST_CONV and HANDOFF and self.resample == 'UP' and kind == 'up' and w.dtype == torch.float32
+                and fast_conv_mod.takes_planes(shape, w.shape, 'up'))
 
     def forward(self, x, cls):
-        h = to_nhwc(self.deconv(to_nchw_view(x)))
-        return _norm_relu(self.bn, h, cls)
+        up = self.resample == 'UP'
+        h = _norm_relu(self.bn, x, cls, self if up else None, 'up')
+        d = self.deconv
+        if up and FAST_CONV and h.is_cuda:
+            y = fast_conv_mod.fast_conv_or_none(h, d.weight, d.bias, 'up', site=self)
+            if y is not None:
+                return y
+        return to_nhwc(d(to_nchw_view(h)))
 
 
 class Generator(nn.Module):
@@ -447,6 +487,8 @@ class Generator(nn.Module):
         self.blocks = nn.ModuleList(blocks)
         self.final_norm = last_norm_layer(axis=-1, name='Generator.BN.Final', channels=ch)
         self.final_conv = conv_layer(ch, output_channels, (3, 3), name='Generator.Final')
+        if arch == 'dcgan':     # (_NarrowConv3x3.backward: the bias gradient without a convolution operator)
+            self.final_conv.sum_bias_grad = True
 
     def forward(self, z, cls=None):
         y = z

@@ -420,6 +420,42 @@ CONFIGS = {'cifar10_uncond': CIFAR10_UNCOND, 'cifar10_cond': CIFAR10_COND, 'stl1
            'tinyimagenet_cond_sa': TINYIMAGENET_COND_SA}
 
 
+
+
+def _dcgan(w, image, filters=512):
+    """scripts/{cifar10,stl10}_dcgan_sn_uncond.sh (--arc dcgan, generator_filters = discriminator_filters = 512, norms d / uconv, SN critic,
+    training_ratio 1, generator_batch_multiple 1) with the widths of run.py:167-171 (generator: F, F/2, F/4, three UP blocks from a
+    (w, w, F) first block) and run.py:213-217 (critic: F/8, F/4, F/4, F/2, F/2, F, F; SAME and DOWN alternating)."""
+    F_ = int(filters)
+    return dict(
+        generator=dict(block_sizes=(F_, F_ // 2, F_ // 4), resamples=("UP", "UP", "UP"), first_block_shape=(w, w, F_),
+                       number_of_classes=10, block_norm='d', block_after_norm='uconv', last_norm='d', last_after_norm='uconv',
+                       gan_type=None, arch='dcgan'),
+        discriminator=dict(input_image_shape=image, block_sizes=(F_ // 8, F_ // 4, F_ // 4, F_ // 2, F_ // 2, F_, F_),
+                           resamples=('SAME', 'DOWN', 'SAME', 'DOWN', 'SAME', 'DOWN', 'SAME'), number_of_classes=10, type=None,
+                           spectral=True, sum_pool=True, conv_singular=False, arch='dcgan'),
+        image_shape=image, conditional=False, training_ratio=1, generator_batch_multiple=1)
+
+
+# the two DCGAN-SN recipes; NOT in CONFIGS (that is BASELINE.json's list, which bench.py takes by name)
+DCGAN_CONFIGS = {'cifar10_dcgan_uncond': _dcgan(4, (32, 32, 3)), 'stl10_dcgan_uncond': _dcgan(6, (48, 48, 3))}
+
+
+def dcgan_sites(config, batch):
+    """(name, N, H, W, C) of every WC site of a DC generator at batch size `batch`: one on each block's INPUT (generator.DCBlockUp is
+    pre-activation), then the final site generator.py:154 -- len(blocks) + 1 in all."""
+    g = config['generator']
+    h, w, c = g['first_block_shape']
+    sites = []
+    for i, (bs, rs) in enumerate(zip(g['block_sizes'], g['resamples'])):
+        sites.append((f'Generator.{i}.bn', batch, h, w, c))
+        if rs == 'UP':
+            h, w = 2 * h, 2 * w
+        c = int(bs)
+    sites.append(('Generator.BN.Final', batch, h, w, c))
+    return sites
+
+
 def baseline_config(config, after_norm='ucs', fused=True):
     """The batch-norm generator the reference sets WC against (run.py:277,285: norm 'b' is its default, after-norm 'ucs'; 'ccs' is the
     conditional batch norm of the cWC comparisons): a copy of a CONFIGS entry with both norms 'b', both after-norms `after_norm`, on
@@ -473,5 +509,8 @@ def build_trainer(config=CIFAR10_UNCOND, device='cuda', process_group=None, sync
     D = make_discriminator(**config['discriminator']).to(device)
     broadcast_state(G, group=process_group)
     broadcast_state(D, group=process_group)
+    for key in ('training_ratio', 'generator_batch_multiple'):        # a recipe's own schedule (DCGAN_CONFIGS), unless the caller overrides it
+        if key in config:
+            kw.setdefault(key, config[key])
     return GanTrainer(G, D, number_of_classes=config['generator']['number_of_classes'],
                       conditional=config['conditional'], process_group=process_group, **kw)
