@@ -97,8 +97,13 @@ size_t wc_whiten_workspace_bytes(int64_t M, int C, int groups);
  * workgroup of the same launch): byte offset into the workspace given to wc_factor_f64 / wc_whiten_f32 of `groups` uint32 words, 64
  * bytes apart, that are 0 after a clean call and 1 when a wait ran out (W then also holds a NaN).  Read them back behind the
  * call (stream order) when the GPU is shared or time-sliced; WC_K2_TWO_LAUNCH=1 selects the form without such a wait.  0: no such
- * launch for this shape. */
+ * launch for this shape (wc_factor_route != 2: other widths, more than 8 groups, WC_K2_TWO_LAUNCH) -- the words are then not written. */
 size_t wc_factor_error_offset(int C, int groups);
+/* Which launch sequence K2 takes for (C, groups) -- the host's own decision, exported so that tests and tools can assert it instead of
+ * restating the gates: 0 = Cholesky + level-doubling inverse (C > 256), 1 = factor with look-ahead + column inverse in two launches
+ * (C < 128, more than 8 groups, or WC_K2_TWO_LAUNCH), 2 = factor and inverse in one launch (the only route with error words).
+ * -1: the shape is refused (wc_factor_workspace_bytes returns 0). */
+int    wc_factor_route(int C, int groups);
 size_t wc_whiten_error_offset(int64_t M, int C, int groups);
 int    wc_whiten_f32(const float* x, int64_t M, int C, int groups, double eps, double momentum, int ddof,
                      float* moving_mean /*[C] in/out, nullable*/, float* moving_cov /*[C,C] in/out, nullable*/,

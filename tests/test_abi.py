@@ -73,6 +73,23 @@ def test_workspace_sizes(lib):
     assert per_sample >= 128 * 128 * 128 * 8 and whole > 0
 
 
+def test_factor_route_and_error_words_follow_the_launch_gate(lib):
+    """wc_factor_route is the host's own K2 decision (csrc/wc_small.hip: use_fused_factor, factor_one_launch), and the one-launch form's
+    error words exist exactly where that form runs: with nine groups the launch is not taken, its counters are never zeroed, and an
+    offset handed out there (as before this check existed) pointed a caller at uninitialised workspace."""
+    assert [lib.wc_factor_route(C, 1) for C in (32, 96, 128, 192, 256, 288, 1024)] == [1, 1, 2, 2, 2, 0, 0]
+    assert lib.wc_factor_route(128, 8) == 2 and lib.wc_factor_route(128, 9) == 1 and lib.wc_factor_route(256, 9) == 1
+    assert lib.wc_factor_route(48, 1) == -1 and lib.wc_factor_route(64, 0) == -1 and lib.wc_factor_route(1056, 1) == -1
+    for C in range(32, 1025, 32):
+        for groups in (1, 8, 9, 40):
+            route, off = lib.wc_factor_route(C, groups), lib.wc_factor_error_offset(C, groups)
+            assert lib.wc_factor_workspace_bytes(C, groups) >= groups * C * C * 8
+            assert route == (0 if C > 256 else 2 if C >= 128 and groups <= 8 else 1), (C, groups)
+            assert off == (groups * C * 16 * 8 + 4 if route == 2 else 0), (C, groups)
+            assert off + 64 * groups <= lib.wc_factor_workspace_bytes(C, groups)
+            assert (lib.wc_whiten_error_offset(4096 * groups, C, groups) != 0) == (route == 2), (C, groups)
+
+
 def test_argument_checks_return_codes_without_touching_the_gpu(lib):
     one = ctypes.c_void_p(16)      # never dereferenced: every call below is rejected first
     assert lib.wc_apply_f32(None, None, None, None, None, 1, 1, 32, 1, None, None, None, 0, None) == -1

@@ -163,12 +163,23 @@ size_t wc_factor_workspace_bytes(int C, int groups)
     return slot_bytes((size_t)groups * C * C, 8);
 }
 
-// K2 in one launch (128 <= C <= 256): the inverse's workgroups wait for the factorising one with a bounded spin; a wait that ran
-// out poisons W with a NaN and sets word [16 g + 1] of the row-block counters (group g) -- `groups` words 64 bytes apart from the
-// returned byte offset into the call's workspace, zero after a clean call.  0: this shape has no such launch (nothing to check).
+// The route wc_factor_f64 (and the K2 half of the wc_whiten_* entries) takes for a shape: 0 = Cholesky, then the level-doubling
+// inverse (C > 256); 1 = factor with look-ahead, then the column inverse: two launches (C < 128, more than 8 groups, or
+// WC_K2_TWO_LAUNCH); 2 = both in one launch.  -1: the shape is refused.  The host's own decision, for tests and tools to assert.
+int wc_factor_route(int C, int groups)
+{
+    if (bad_channels(C) || groups <= 0) return -1;
+    return wc_factor_route_of(C, groups);
+}
+
+// K2 in one launch (128 <= C <= 256, at most 8 groups): the inverse's workgroups wait for the factorising one with a bounded spin; a
+// wait that ran out poisons W with a NaN and sets word [16 g + 1] of the row-block counters (group g) -- `groups` words 64 bytes apart
+// from the returned byte offset into the call's workspace, zero after a clean call.  0: this shape has no such launch (nothing to check;
+// the words are then not written at all -- until this followed the launch's own gate, a caller that read them behind a call with nine
+// groups read whatever the workspace held).
 size_t wc_factor_error_offset(int C, int groups)
 {
-    if (bad_channels(C) || groups <= 0 || !wc_factor_is_fused(C) || C < 128 || C > 256) return 0;
+    if (wc_factor_route(C, groups) != 2) return 0;
     return (size_t)groups * C * 16 * 8 + 4;
 }
 

@@ -284,6 +284,7 @@ hipError_t wc_launch_factor_prepare(const double* sum, const double* xtx, int64_
 // C <= 256: L (in place on T, upper zeroed) and W = L^-1 in one launch (two for many groups); tmp: [groups][C*16] doubles + 64 B
 // per group at least, the SAME tmp that wc_launch_factor_prepare was given (it zeroes the launch's row-block counters there)
 bool wc_factor_is_fused(int C);
+int wc_factor_route_of(int C, int groups);      // 0: wc_launch_cholesky + wc_launch_tri_inverse; 1: wc_launch_factor_fused in two launches; 2: in one
 hipError_t wc_launch_factor_fused(double* T, double* W, double* tmp, int C, int groups, hipStream_t st);
 hipError_t wc_launch_cholesky(double* T, int C, int groups, hipStream_t st);                     // in place: lower factor, upper zeroed
 hipError_t wc_launch_tri_inverse(const double* L, double* W, double* tmp, int C, int groups, hipStream_t st);   // W = L^-1 (lower), upper zeroed

@@ -1864,6 +1864,7 @@ hipError_t wc_launch_factor_fused(double* T, double* W, double* tmp, int C, int 
 }
 
 bool wc_factor_is_fused(int C) { return use_fused_factor(C); }
+int wc_factor_route_of(int C, int groups) { return !use_fused_factor(C) ? 0 : factor_one_launch(C, groups) ? 2 : 1; }
 
 hipError_t wc_launch_cholesky(double* T, int C, int groups, hipStream_t st)
 {
