@@ -809,6 +809,32 @@ int    wc_bwd_factor_renorm_f64(const double* R, const double* gsum, const doubl
                                 float* S /*[C,C]*/, float* gmean /*[C]*/,
                                 void* ws, size_t ws_bytes, wc_stream_t stream);
 
+/* ==== gradient penalty of the WGAN-GP recipes (scripts/cifar10_resnet_wgan_*.sh, --gradinet_penalty_weight) ================================
+ * Additive like the blocks above: WC_CORE_API keeps its list and WC_ABI_VERSION its value.  The penalty's weight gradient is the weight
+ * gradient of a tangent pass through the critic with the primal pass's ReLU decisions frozen: it runs on
+ * wc_conv_f16x3 / wc_conv_wrw_f16x3 and the narrow-input entries; these are the pieces around them.  All stream-ordered and
+ * graph-capturable; nothing allocates. */
+
+/* The operand split of a tangent: planes of t[i] * (a[i] > 0 ? 1 : slope), a = the primal pre-activation (fp32, t's shape), 0 <= slope <= 1
+ * (0: the ResNet critic's ReLU; the DC critic's LeakyReLU is 0.3).  (hi, lo, scale), the scale rule, the `hist` record, `bootstrap` and the
+ * gated second pass are those of wc_conv_split_f32 / wc_conv_split_hist_f32: the planes and the scale are bit for bit what those entries
+ * give for the premultiplied fp32 tensor, without that tensor.  n % 4 == 0. */
+int wc_conv_split_masked_f32(const float* t, const float* a, int64_t n, float slope, void* hi, void* lo, float* scale, void* amax_scratch,
+                             wc_stream_t stream);
+int wc_conv_split_hist_masked_f32(const float* t, const float* a, int64_t n, float slope, void* hi, void* lo, float* scale, float* hist,
+                                  int bootstrap, wc_stream_t stream);
+
+/* x_hat[n] = eps[n] real[n] + (1 - eps[n]) fake[n] for N samples of L floats, eps [N] on the device (formed in float64, rounded once). */
+int wc_gp_interp_f32(const float* real, const float* fake, const float* eps, int64_t N, int64_t L, float* x_hat, wc_stream_t stream);
+
+/* For the input gradients g [N, L] of the critic:  norms[n] = ||g_n||_2,  v[n] = 2 lambda inv_n (1 - 1 / norms[n]) g[n]  (a zero row gives
+ * v = 0, the subgradient torch's norm takes),  *penalty = lambda inv_n sum_n (norms[n] - 1)^2.  Sums of squares in float64 (rows of
+ * magnitude 1e-20 or 1e+15 stay finite), one workgroup per sample, the N-term finish in a fixed order: the same bits on every call.
+ * `ws`: wc_gp_rows_workspace_bytes(N) device bytes. */
+size_t wc_gp_rows_workspace_bytes(int64_t N);
+int wc_gp_rows_f32(const float* g, int64_t N, int64_t L, double lambda, double inv_n, float* norms /*[N]*/, float* v /*[N,L]*/,
+                   float* penalty /*[1]*/, void* ws, size_t ws_bytes, wc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

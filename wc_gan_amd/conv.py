@@ -163,18 +163,20 @@ HIST_REDO = 4 * 512            # WC_CONV_HIST_REDO: uint32 count of the gated se
 
 
 # The gated second pass of the history-scaled split (include/wc_hip.h, wc_conv_split_hist_f32): WC_SPLIT_HIST_REDO = 1 (default) for the
-# output gradients only, 2 for every split, 0 for none.  (Every split of the step: +0.56 ms of 18 -- what the history saves.)
+# output gradients only (role 'g', and the gradient penalty's 't' and 'd'), 2 for every split, 0 for none.  (Every split of the step: +0.56 ms of 18 -- what the history saves.)
 _REDO_MODE = os.environ.get('WC_SPLIT_HIST_REDO', '1')
 
 
 def _guarded(role):
-    return _REDO_MODE == '2' or (_REDO_MODE != '0' and role == 'g')
+    # 't' / 'd': the tangents and adjoints of the gradient penalty (penalty.py) scale with | ||grad D|| - 1 |: orders of magnitude between calls
+    return _REDO_MODE == '2' or (_REDO_MODE != '0' and role in ('g', 't', 'd'))
 
 
 def _site_hist(site, role, device):
     """[record (HIST_FLOATS floats on the device: two arrays of per-workgroup (maximum, tag) pairs), seeded?] of a call site:
     `site` is the layer object that owns the convolution (state lives in its __dict__, not in a parameter or buffer: no checkpoint entry --
-    a resumed run measures once), role 'x' (its input) or 'g' (its output gradient).  None for a layer in eval mode, and while a hipGraph is
+    a resumed run measures once), role 'x' (its input) or 'g' (its output gradient); the gradient penalty (penalty.py) keeps records of its own
+    at the same sites -- 'p' (the primal input at the interpolates), 't' (the tangent), 'd' (the adjoint) -- so that 'x' and 'g' never see it.  None for a layer in eval mode, and while a hipGraph is
     being recorded for a site that has no record yet (no allocation into a graph's private pool; the trainers warm up eagerly first)."""
     if not getattr(site, 'training', True):
         return None
@@ -237,6 +239,28 @@ def _split_planes_leaky(lib, x, slope, colsum, site, role):
         _lib.check(lib.wc_conv_split_leaky_f32(_ptr(x), x.numel(), slope, _ptr(hi), _ptr(lo), _ptr(scale), scale.data_ptr() + 4,
                                                _ptr(part), C if colsum else 0, _stream()), "wc_conv_split_leaky_f32")
     return (hi, lo, scale, part) if colsum else (hi, lo, scale)
+
+
+def split_planes_masked(t, a, slope=0.0, site=None, role='t'):
+    """(hi, lo, scale) of t * (a > 0 ? 1 : slope) -- a tangent behind a ReLU (slope 0) or LeakyReLU whose primal pre-activation was `a` --
+    in the launches of split_planes and with its bits on the premultiplied tensor (wc_conv_split[_hist]_masked_f32, csrc/wc_gp.hip).
+    site / role as in split_planes; role 't' takes the gated second pass."""
+    if not (t.is_contiguous() and a.is_contiguous() and t.shape == a.shape and t.dtype == a.dtype == torch.float32):
+        raise ValueError("split_planes_masked: dense fp32 tensors of one shape")
+    lib = _lib.load()
+    both = torch.empty((2,) + tuple(t.shape), dtype=torch.float16, device=t.device)
+    hi, lo = both[0], both[1]
+    scale = torch.empty(1 + 512, dtype=torch.float32, device=t.device)
+    h = _site_hist(site, role, t.device) if (SPLIT_HIST and site is not None) else None
+    if h is not None:
+        _lib.check(lib.wc_conv_split_hist_masked_f32(_ptr(t), _ptr(a), t.numel(), float(slope), _ptr(hi), _ptr(lo), _ptr(scale), _ptr(h[0]),
+                                                     (0 if h[1] else 1) | (0 if _guarded(role) else 2), _stream()),
+                   "wc_conv_split_hist_masked_f32")
+        h[1] = True
+    else:
+        _lib.check(lib.wc_conv_split_masked_f32(_ptr(t), _ptr(a), t.numel(), float(slope), _ptr(hi), _ptr(lo), _ptr(scale),
+                                                scale.data_ptr() + 4, _stream()), "wc_conv_split_masked_f32")
+    return hi, lo, scale
 
 
 def leaky_backward_(dx, x, slope):
@@ -577,6 +601,24 @@ class _NarrowInConv(torch.autograd.Function):
             _lib.check(lib.wc_conv_wrw_narrow64_f32(_ptr(xc), _ptr(g), N, H, W, C, O, k, _ptr(dw), dw.stride(1), dw.stride(0), dw.stride(2),
                                                     dw.stride(3), _ptr(db), _ptr(ws), nb, _stream()), "wc_conv_wrw_narrow64_f32")
         return dx, dw, db
+
+
+def narrow_weight_gradient(x, gy, w):
+    """dW (w's own strides) of the 'same' convolution of an image-like NHWC x (narrow_wrw_supported) from its fp32 output gradient: the
+    launch of _NarrowInConv.backward without the bias gradient"""
+    N, H, W, C = x.shape
+    O, k = w.shape[0], w.shape[2]
+    lib = _lib.load()
+    dw = torch.empty_strided(w.shape, w.stride(), dtype=torch.float32, device=w.device)
+    if _storage_extent(dw) != dw.numel():
+        raise ValueError("weight must be dense")
+    nb = lib.wc_conv_wrw_narrow64_workspace_bytes(N, H, W, C, O, k)
+    ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    xc = x if x.is_contiguous() else x.contiguous()
+    g = gy if gy.is_contiguous() else gy.contiguous()
+    _lib.check(lib.wc_conv_wrw_narrow64_f32(_ptr(xc), _ptr(g), N, H, W, C, O, k, _ptr(dw), dw.stride(1), dw.stride(0), dw.stride(2),
+                                            dw.stride(3), None, _ptr(ws), nb, _stream()), "wc_conv_wrw_narrow64_f32")
+    return dw
 
 
 def narrow_in_conv(x, w, bias=None):

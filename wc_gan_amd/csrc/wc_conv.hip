@@ -373,6 +373,8 @@ __global__ __launch_bounds__(256) void conv_split_kernel(const float* __restrict
 // relaxed device-scope atomics the 1024 operations on one cache line serialise, 15.4 us against 7.1 for both launches of the measuring
 // form at 128x4x4x256.)  NOTHING clamps: an element that does not fit becomes inf in the planes and NaN / inf in the convolution's
 // output -- loud, never quietly wrong.  The first call of a site measures (the two-launch form) and seeds the record.
+// (csrc/wc_gp.hip restates this record protocol -- seed, history split, gated second pass, these constants -- around a two-tensor load:
+// change both; tests/test_penalty_gpu.py compares the planes, the scales and the records bit for bit)
 constexpr float kHistMargin = 64.0f;
 constexpr int kHistArray = 2 * kAmaxBlocks;         // floats per array: (maximum, tag) per workgroup
 

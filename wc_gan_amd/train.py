@@ -37,7 +37,9 @@ class FlatGradBucket:
             return
         n = sum(p.numel() for p in self.params)
         dev = self.params[0].device
-        self.flat = torch.zeros(n, dtype=torch.float32, device=dev)
+        if len({p.dtype for p in self.params}) != 1:
+            raise ValueError("FlatGradBucket: the parameters of one network share one dtype")
+        self.flat = torch.zeros(n, dtype=self.params[0].dtype, device=dev)      # (float32 everywhere but in float64 tests)
         off = 0
         for p in self.params:
             seg = self.flat[off:off + p.numel()]
@@ -119,7 +121,13 @@ def _bump_versions(params):
 class GanTrainer:
     def __init__(self, generator, discriminator, batch_size=64, generator_batch_multiple=2, training_ratio=5,
                  lr=2e-4, beta1=0.0, beta2=0.9, noise_dim=128, number_of_classes=10, conditional=False,
-                 process_group=None, seed=1234, flat_buckets=None):
+                 process_group=None, seed=1234, flat_buckets=None, objective='hinge', gradient_penalty_weight=0.0):
+        if objective not in ('hinge', 'wgan'):
+            raise ValueError(f"objective {objective!r}: 'hinge' or 'wgan' (run.py --*_adversarial_objective)")
+        # 'wgan' (scripts/cifar10_resnet_wgan_*.sh): the critic loss E D(fake) - E D(real), plus gradient_penalty_weight x the gradient
+        # penalty at interpolates of the two batches (penalty.py: closed form, no second-order autograd)
+        self.objective, self.gp_weight = objective, float(gradient_penalty_weight)
+        self.last_penalty = self.last_grad_norms = None
         self.G, self.D = generator, discriminator
         self.batch_size, self.gbm, self.training_ratio = batch_size, generator_batch_multiple, training_ratio
         self.noise_dim, self.K, self.conditional = noise_dim, number_of_classes, conditional
@@ -178,7 +186,8 @@ class GanTrainer:
             fake = self.G(z, cls)                      # train-mode WC forward (batch statistics), no graph
         return fake.split(self.batch_size), cls.split(self.batch_size)
 
-    def d_step(self, real, real_cls=None, fake=None, cls=None):
+    def d_step(self, real, real_cls=None, fake=None, cls=None, eps=None):
+        """One critic update.  eps: the (N,) interpolation weights of the gradient penalty (drawn on the device when None)."""
         if fake is None:
             (fake,), (cls,) = self.generate(1)
         self.d_bucket.zero()
@@ -193,12 +202,23 @@ class GanTrainer:
         else:
             both_cls = None
         out = self._d(torch.cat([real, fake], dim=0), both_cls)
-        loss = F.relu(1.0 - out[:n]).mean() + F.relu(1.0 + out[n:]).mean()
+        if self.objective == 'wgan':
+            loss = out[n:].mean() - out[:n].mean()
+        else:
+            loss = F.relu(1.0 - out[:n]).mean() + F.relu(1.0 + out[n:]).mean()
         loss.backward()
+        loss = loss.detach()
+        if self.gp_weight != 0.0:
+            # into the same .grad tensors (the flat bucket's views), ahead of the all-reduce
+            from .penalty import gradient_penalty, interpolate
+            x_hat = interpolate(real, fake, eps)
+            hat_cls = both_cls[:n] if self.conditional else None        # a projection critic sees the interpolate under the real batch's labels
+            self.last_penalty, self.last_grad_norms = gradient_penalty(self.D, x_hat, hat_cls, self.gp_weight)
+            loss = loss + self.last_penalty
         self._sync_grads(self.d_bucket)
         self.opt_d.step()
         _bump_versions(self.d_bucket.params)
-        return loss.detach()
+        return loss
 
     def g_step(self, generated=None):
         self.g_bucket.zero()
@@ -440,6 +460,16 @@ def _dcgan(w, image, filters=512):
 # the two DCGAN-SN recipes; NOT in CONFIGS (that is BASELINE.json's list, which bench.py takes by name)
 DCGAN_CONFIGS = {'cifar10_dcgan_uncond': _dcgan(4, (32, 32, 3)), 'stl10_dcgan_uncond': _dcgan(6, (48, 48, 3))}
 
+# scripts/cifar10_resnet_wgan_uncond.sh: --generator_adversarial_objective wgan --discriminator_adversarial_objective wgan
+# --gradinet_penalty_weight 10, generator_filters = discriminator_filters = 128, norms d / uconv, no spectral normalisation, critic norm 'n'.
+# NOT in CONFIGS either.  (The two conditional WGAN scripts use an AC_GAN critic, whose classification loss no recipe here trains yet.)
+WGAN_CONFIGS = {'cifar10_wgan_uncond': dict(
+    generator=dict(block_sizes=(128, 128, 128), resamples=("UP", "UP", "UP"), first_block_shape=(4, 4, 128),
+                   number_of_classes=10, block_norm='d', block_after_norm='uconv', last_norm='d', last_after_norm='uconv', gan_type=None),
+    discriminator=dict(input_image_shape=(32, 32, 3), block_sizes=(128, 128, 128, 128), resamples=('DOWN', 'DOWN', 'SAME', 'SAME'),
+                       number_of_classes=10, type=None, spectral=False, sum_pool=True),
+    image_shape=(32, 32, 3), conditional=False, objective='wgan', gradient_penalty_weight=10)}
+
 
 def dcgan_sites(config, batch):
     """(name, N, H, W, C) of every WC site of a DC generator at batch size `batch`: one on each block's INPUT (generator.DCBlockUp is
@@ -509,7 +539,8 @@ def build_trainer(config=CIFAR10_UNCOND, device='cuda', process_group=None, sync
     D = make_discriminator(**config['discriminator']).to(device)
     broadcast_state(G, group=process_group)
     broadcast_state(D, group=process_group)
-    for key in ('training_ratio', 'generator_batch_multiple'):        # a recipe's own schedule (DCGAN_CONFIGS), unless the caller overrides it
+    # a recipe's own schedule (DCGAN_CONFIGS) and objective (WGAN_CONFIGS), unless the caller overrides them
+    for key in ('training_ratio', 'generator_batch_multiple', 'objective', 'gradient_penalty_weight'):
         if key in config:
             kw.setdefault(key, config[key])
     return GanTrainer(G, D, number_of_classes=config['generator']['number_of_classes'],
