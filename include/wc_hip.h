@@ -686,6 +686,23 @@ int wc_conv_wrw_bias_f16x3(const void* xhi, const void* xlo, const float* xscale
                            int64_t stride_n, int64_t stride_r, int64_t stride_s, const float* colsum_partials, float* db,
                            void* ws, size_t ws_bytes, wc_stream_t stream);
 
+/* One layer's backward in two launches instead of four: wc_conv_f16x3(gy planes, data-gradient image, gd, no bias, no ReLU) -> dx and
+ * wc_conv_wrw_bias_f16x3(x planes, gy planes, gf) -> dw (, db) with the workgroups of both in ONE grid and one launch that finishes both
+ * (the weight reduction, the bias gradient and -- where the data gradient is k-split -- its reduction).  Every workgroup runs what it runs
+ * in the two entries, on the same operands, and the reductions keep their order: dx, dw and db have the bits of the two calls.
+ * gd / gf: the data-gradient and the forward geometry of the layer.  wc_conv_bwd_pair_supported: both gradients on 128 x 128 tiles
+ * (128-channel layers whose data gradient gives at most ~256 workgroups) of a 'same' or stride-2 down-sampling layer; everything else stays
+ * on the two calls.  ws_dx: wc_conv_workspace_bytes(gd) bytes (may be NULL when that is 0), ws_dw: wc_conv_wrw_workspace_bytes(gf) bytes;
+ * wc_conv_bwd_pair_workspace_bytes is their sum.  colsum_partials / db: both or neither, as in wc_conv_wrw_bias_f16x3.  Additive: WC_CORE_API
+ * keeps its list and WC_ABI_VERSION its value. */
+int    wc_conv_bwd_pair_supported(const wc_conv_geom* gd, const wc_conv_geom* gf);
+size_t wc_conv_bwd_pair_workspace_bytes(const wc_conv_geom* gd, const wc_conv_geom* gf);
+int    wc_conv_bwd_pair_f16x3(const void* ghi, const void* glo, const float* gscale, const void* wimage, const float* wscale,
+                              const void* zero_line, const wc_conv_geom* gd, float* dx, void* ws_dx, size_t ws_dx_bytes,
+                              const void* xhi, const void* xlo, const float* xscale, const wc_conv_geom* gf, float* dw,
+                              int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
+                              const float* colsum_partials, float* db, void* ws_dw, size_t ws_dw_bytes, wc_stream_t stream);
+
 /* Bandwidth yardstick used by bench.py: dst[i] = src[i] (float4 grid-stride copy), same stream rules. */
 int wc_stream_copy_f32(const float* src, float* dst, int64_t n, wc_stream_t stream);
 

@@ -160,6 +160,11 @@ SIGNATURES = {
     "wc_conv_workspace_bytes": (c_size_t, [c_void_p]),
     "wc_conv_f16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                               c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wc_conv_bwd_pair_supported": (c_int, [c_void_p, c_void_p]),
+    "wc_conv_bwd_pair_workspace_bytes": (c_size_t, [c_void_p, c_void_p]),
+    "wc_conv_bwd_pair_f16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                       c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "wc_std_stats_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "wc_std_stats_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "wc_std_factor_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_double, c_double, c_int, c_int, c_void_p, c_void_p,

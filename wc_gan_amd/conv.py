@@ -111,7 +111,7 @@ def supported(x, w, kind):
 class _Plan:
     """Everything about a call that depends on the shapes only, built once: the two geometries, the weight axes, the
     support verdict and the workspace sizes (the per-call host work is what is left: a few allocations and launches)."""
-    __slots__ = ('ok', 'fwd', 'bwd', 'fwd_ws', 'bwd_ws', 'wrw_ws', 'fwd_ptr', 'bwd_ptr')
+    __slots__ = ('ok', 'fwd', 'bwd', 'fwd_ws', 'bwd_ws', 'wrw_ws', 'fwd_ptr', 'bwd_ptr', 'pair')
 
     def __init__(self, kind, N, H, W, wshape):
         class _W:                                   # shape-only stand-in for the weight
@@ -124,6 +124,8 @@ class _Plan:
         self.fwd_ws = lib.wc_conv_workspace_bytes(self.fwd_ptr) if self.ok else 0
         self.bwd_ws = lib.wc_conv_workspace_bytes(self.bwd_ptr) if self.ok else 0
         self.wrw_ws = lib.wc_conv_wrw_workspace_bytes(self.fwd_ptr) if self.ok else 0
+        # data gradient and weight gradient in one grid (wc_conv_bwd_pair_f16x3): the critic's 128-channel layers
+        self.pair = self.ok and bool(lib.wc_conv_bwd_pair_supported(self.bwd_ptr, self.fwd_ptr))
 
 
 _plans = {}
@@ -378,6 +380,31 @@ def weight_gradient(x_planes, g_planes, geom, w, k_axis, n_axis, nbytes=None, co
     return dw
 
 
+def backward_pair(g_planes, image, x_planes, plan, w, colsum=None):
+    """run(g_planes, image, plan.bwd) and weight_gradient(x_planes, g_planes, plan.fwd, w, ...) of one layer in two launches
+    (wc_conv_bwd_pair_f16x3; plan.pair says whether the library takes the layer): -> (dx, dW, db | None), the bits of the two calls."""
+    lib = _lib.load()
+    gh, gl, gs = g_planes[:3]
+    xh, xl, xs = x_planes
+    img, ws = image
+    gf, kf, nf = plan.fwd
+    gb = plan.bwd[0]
+    dx = torch.empty((gb.N, gb.Hout, gb.Wout, gb.Cout), dtype=torch.float32, device=gh.device)
+    dw = torch.empty_like(w)
+    if dw.stride() != w.stride():
+        raise ValueError("weight must be dense")
+    work_dx = torch.empty(plan.bwd_ws, dtype=torch.uint8, device=gh.device) if plan.bwd_ws else None
+    work_dw = torch.empty(plan.wrw_ws, dtype=torch.uint8, device=gh.device)
+    db = torch.empty(gf.Cout, dtype=torch.float32, device=w.device) if colsum is not None else None
+    zero = _zero_line(gh.device)
+    _lib.check(lib.wc_conv_bwd_pair_f16x3(_ptr(gh), _ptr(gl), _ptr(gs), _ptr(img), _ptr(ws), _ptr(zero), plan.bwd_ptr, _ptr(dx),
+                                          _ptr(work_dx), plan.bwd_ws,
+                                          _ptr(xh), _ptr(xl), _ptr(xs), plan.fwd_ptr, _ptr(dw), w.stride(kf), w.stride(nf), w.stride(2),
+                                          w.stride(3), _ptr(colsum), _ptr(db), _ptr(work_dw), plan.wrw_ws, _stream()),
+               "wc_conv_bwd_pair_f16x3")
+    return dx, dw, db
+
+
 def takes_planes(shape, wshape, kind):
     """Would fast_conv_or_none take an input of this NHWC shape as planes handed over by K3 (functional.whiten_color(planes=True))?
     Shapes only -- the caller asks before it runs the site."""
@@ -418,15 +445,22 @@ class _FastConv(torch.autograd.Function):
         fused_db = want_db and ctx.needs_input_grad[1] and _colsum_ok(gy.shape[-1])    # db rides on the split + the dW reduction
         g_planes = split_planes(gy, colsum=fused_db, site=ctx.site, role='g')
         dx = dw = db = None
+        # both gradients wanted, the data gradient's image at hand, a layer the pair entry takes: one grid for the two
+        paired = ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and ctx.bwd_image is not None and plan.pair
+        if paired:
+            dx, dw, pdb = backward_pair(g_planes, ctx.bwd_image, (xh, xl, xs), plan, w, colsum=g_planes[3] if fused_db else None)
+            if fused_db:
+                db = pdb
         if ctx.needs_input_grad[0]:
-            gb, kb, nb = plan.bwd
-            image = ctx.bwd_image if ctx.bwd_image is not None else weight_image(w, gb, kb, nb)
-            dx = run(g_planes[:3], image, gb, nbytes=plan.bwd_ws)
+            if not paired:
+                gb, kb, nb = plan.bwd
+                image = ctx.bwd_image if ctx.bwd_image is not None else weight_image(w, gb, kb, nb)
+                dx = run(g_planes[:3], image, gb, nbytes=plan.bwd_ws)
             if ctx.relu_input:
                 dx = torch.ops.aten.threshold_backward(dx, ctx.saved_tensors[4], 0)
             elif ctx.leaky is not None:
                 dx = leaky_backward_(dx, ctx.saved_tensors[4], ctx.leaky)
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] and not paired:
             gf, kf, nf = plan.fwd
             if fused_db:
                 dw, db = weight_gradient((xh, xl, xs), g_planes, gf, w, kf, nf, nbytes=plan.wrw_ws, colsum=g_planes[3])
@@ -486,18 +520,25 @@ class _SplitConv(torch.autograd.Function):
         fused_db = need_w and _colsum_ok(gy.shape[-1])       # db rides on the split + the dW reduction (the unfolding needs it anyway)
         g_planes = split_planes(gy, colsum=fused_db, site=ctx.site, role='g')
         dx = dw = db = None
-        if ctx.needs_input_grad[0]:
+        paired = ctx.needs_input_grad[0] and need_w and ctx.bwd_image is not None and plan.pair
+        if paired:
+            dx, D, db = backward_pair(g_planes, ctx.bwd_image, (xh, xl, one), plan, w, colsum=g_planes[3] if fused_db else None)
+            if not fused_db:
+                db = gy.sum((0, 1, 2))
+            dw = ops.unfold_channel_scale(D, db, scale, center)
+        elif ctx.needs_input_grad[0]:
             gb, kb, nb = plan.bwd
             image = ctx.bwd_image if ctx.bwd_image is not None else weight_image(w, gb, kb, nb)
             dx = run(g_planes[:3], image, gb, nbytes=plan.bwd_ws)
         if need_w:
-            gf, kf, nf = plan.fwd
-            if fused_db:
-                D, db = weight_gradient((xh, xl, one), g_planes, gf, w, kf, nf, nbytes=plan.wrw_ws, colsum=g_planes[3])
-            else:
-                D = weight_gradient((xh, xl, one), g_planes, gf, w, kf, nf, nbytes=plan.wrw_ws)
-                db = gy.sum((0, 1, 2))
-            dw = ops.unfold_channel_scale(D, db, scale, center)
+            if not paired:
+                gf, kf, nf = plan.fwd
+                if fused_db:
+                    D, db = weight_gradient((xh, xl, one), g_planes, gf, w, kf, nf, nbytes=plan.wrw_ws, colsum=g_planes[3])
+                else:
+                    D = weight_gradient((xh, xl, one), g_planes, gf, w, kf, nf, nbytes=plan.wrw_ws)
+                    db = gy.sum((0, 1, 2))
+                dw = ops.unfold_channel_scale(D, db, scale, center)
         elif need_b:
             db = gy.sum((0, 1, 2))
         return dx, dw, (db if need_b else None), None, None, None

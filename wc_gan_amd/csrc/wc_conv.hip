@@ -24,6 +24,9 @@
 //   * weight gradient: conv_wrw_kernel (pixel-major tiles, ds_read_b64_tr_b16 fragments, split over pixel ranges) +
 //     conv_wrw_reduce_kernel (fixed-order sum into the weight's layout, 4x4 slices folded back onto 3x3 taps); 256 x 256, 128 x 128 or
 //     -- a 64-channel side -- 64 x 64 tiles.
+//   * one layer's backward where both gradients run on 128 x 128 tiles (the critic's 128-channel layers): the data gradient's and the
+//     weight gradient's workgroups in ONE grid (conv_bwd_pair_kernel) and one launch that finishes both (conv_pair_reduce_kernel) --
+//     the kernels' bodies are __device__ functions of the block coordinates, shared with the launches of their own; same bits.
 //   * conv(relu(x)) and conv(leaky_relu(x)) apply the activation while x is split (conv_split_*_kernel, split_act).
 // MFMA-bound by design: 3 * 2*M*Cout*K flop on the fp16 pipe against 2*M*Cout*K on the fp32 pipe (157 TFLOP/s peak).
 #include "wc_common.h"
@@ -56,8 +59,9 @@ __device__ __forceinline__ void lds_dma16(const void* g, unsigned lds)
                  : "=&s"(keep) : "v"(g), "s"(lds) : "memory");
 }
 
+// (the body takes the workgroup's grid coordinates as arguments: conv_bwd_pair_kernel runs it on a range of a linear grid)
 template <int MB, int NB, bool KS>
-__global__ __launch_bounds__(256) void conv_f16x3_kernel(ConvArgs a)
+__device__ __forceinline__ void conv_f16x3_body(const ConvArgs& a, const unsigned bx, const unsigned by, const unsigned bz)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int TM = 64 * MB, TN = 64 * NB;
@@ -69,8 +73,8 @@ __global__ __launch_bounds__(256) void conv_f16x3_kernel(ConvArgs a)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int ntn = a.Cout / TN;
-    const int phase = blockIdx.y / ntn, nt = blockIdx.y - phase * ntn;
-    const unsigned m0 = blockIdx.x * TM;
+    const int phase = by / ntn, nt = by - phase * ntn;
+    const unsigned m0 = bx * TM;
     const unsigned HW = a.H * a.W;
     const int koff = (lane >> 5) * 8;
 
@@ -122,7 +126,7 @@ __global__ __launch_bounds__(256) void conv_f16x3_kernel(ConvArgs a)
             #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    const int it0 = KS ? (int)blockIdx.z * iters / a.ksplit : 0, it1 = KS ? ((int)blockIdx.z + 1) * iters / a.ksplit : iters;
+    const int it0 = KS ? (int)bz * iters / a.ksplit : 0, it1 = KS ? ((int)bz + 1) * iters / a.ksplit : iters;
     // Hand-placed iteration: the fragments of k-step 0 right behind the barrier, then the MFMAs of both k-steps with the
     // next iteration's DMAs (one every GAP MFMAs) and the fragment reads of k-step 1 in their shadow -- the wave issues
     // in order, so whatever stands between the barrier and the first MFMA is time the MFMA pipe idles.
@@ -223,7 +227,7 @@ __global__ __launch_bounds__(256) void conv_f16x3_kernel(ConvArgs a)
             const int64_t opix = ((int64_t)n * a.Hout + (yy * a.out_stride + oy0)) * a.Wout + (xx * a.out_stride + ox0);
             const int64_t oe = opix * a.Cout + nt * TN + wn * NB * 32 + (lane & 31);
             if (KS) {                               // raw partial sums; conv_ksplit_reduce_kernel finishes
-                float* o = a.partial + (int64_t)blockIdx.z * ((int64_t)a.N * a.Hout * a.Wout * a.Cout) + oe;
+                float* o = a.partial + (int64_t)bz * ((int64_t)a.N * a.Hout * a.Wout * a.Cout) + oe;
                 #pragma unroll
                 for (int j = 0; j < NB; ++j) o[j * 32] = acc[i][j][r];
             } else {
@@ -239,13 +243,22 @@ __global__ __launch_bounds__(256) void conv_f16x3_kernel(ConvArgs a)
     }
 }
 
+template <int MB, int NB, bool KS>
+__global__ __launch_bounds__(256) void conv_f16x3_kernel(ConvArgs a) { conv_f16x3_body<MB, NB, KS>(a, blockIdx.x, blockIdx.y, blockIdx.z); }
+
 // ---- small grids: the (tap, chunk) loop split over blockIdx.z; y = (sum of the partial sums) / (sx*sw) + bias ---------
-__global__ __launch_bounds__(256) void conv_ksplit_reduce_kernel(const float* __restrict__ partial, int ksplit, int64_t n4, int cout,
-                                                                 const float* __restrict__ xscale, const float* __restrict__ wscale,
-                                                                 const float* __restrict__ bias, int relu, float* __restrict__ y)
+struct KsplitReduceArgs {
+    const float* partial; int ksplit; int64_t n4; int cout;
+    const float* xscale; const float* wscale; const float* bias; int relu; float* y;
+};
+
+__device__ __forceinline__ void conv_ksplit_reduce_body(const float* __restrict__ partial, int ksplit, int64_t n4, int cout,
+                                                        const float* __restrict__ xscale, const float* __restrict__ wscale,
+                                                        const float* __restrict__ bias, int relu, float* __restrict__ y,
+                                                        const unsigned bid, const unsigned nblocks)
 {
     const float inv = 1.0f / (xscale[0] * wscale[0]);
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    for (int64_t i = (int64_t)bid * 256 + threadIdx.x; i < n4; i += (int64_t)nblocks * 256) {
         f32x4 v = *reinterpret_cast<const f32x4*>(partial + 4 * i);
         int z = 1;
         for (; z + 3 < ksplit; z += 4) {                 // four shares in flight, added in order
@@ -261,6 +274,13 @@ __global__ __launch_bounds__(256) void conv_ksplit_reduce_kernel(const float* __
         if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
         *reinterpret_cast<f32x4*>(y + 4 * i) = v;
     }
+}
+
+__global__ __launch_bounds__(256) void conv_ksplit_reduce_kernel(const float* __restrict__ partial, int ksplit, int64_t n4, int cout,
+                                                                 const float* __restrict__ xscale, const float* __restrict__ wscale,
+                                                                 const float* __restrict__ bias, int relu, float* __restrict__ y)
+{
+    conv_ksplit_reduce_body(partial, ksplit, n4, cout, xscale, wscale, bias, relu, y, blockIdx.x, gridDim.x);
 }
 
 // the activation in front of a split: relu 0 = none, 1 = ReLU, 2 = LeakyReLU (x > 0 ? x : slope * x, one fp32 multiply; Keras's
@@ -648,7 +668,7 @@ __device__ __forceinline__ f16x8 tr_read8(const char* block, int lane_off)
 }
 
 template <int MB, int NB>
-__global__ __launch_bounds__(256) void conv_wrw_kernel(WrwArgs a)
+__device__ __forceinline__ void conv_wrw_body(const WrwArgs& a, const unsigned bx, const unsigned by)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int TA = 64 * MB, TB = 64 * NB;
@@ -663,11 +683,11 @@ __global__ __launch_bounds__(256) void conv_wrw_kernel(WrwArgs a)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int nta = a.A.C / TA, ntb = a.B.C / TB;
-    int idx = blockIdx.y;
+    int idx = by;
     const int tb = idx % ntb; idx /= ntb;
     const int ta = idx % nta; idx /= nta;
     const int tap = idx % a.ntaps, phase = idx / a.ntaps;
-    const int c0 = blockIdx.x * a.cps, c1 = min(c0 + a.cps, a.nchunks);
+    const int c0 = bx * a.cps, c1 = min(c0 + a.cps, a.nchunks);
     const int dya = a.A.dy[phase][tap], dxa = a.A.dx[phase][tap], dyb = a.B.dy[phase][tap], dxb = a.B.dx[phase][tap];
     const unsigned HW = a.H * a.W;
     const unsigned lds0 = (unsigned)(size_t)((__attribute__((address_space(3))) char*)smem);
@@ -816,7 +836,7 @@ __global__ __launch_bounds__(256) void conv_wrw_kernel(WrwArgs a)
     __builtin_amdgcn_s_waitcnt(0x0F70);
 
     const int slice = phase * a.ntaps + tap, nslice = a.nphase * a.ntaps;
-    float* out = a.partial + ((int64_t)blockIdx.x * nslice + slice) * a.A.C * a.B.C;
+    float* out = a.partial + ((int64_t)bx * nslice + slice) * a.A.C * a.B.C;
     #pragma unroll
     for (int i = 0; i < MB; ++i)
         #pragma unroll
@@ -828,6 +848,9 @@ __global__ __launch_bounds__(256) void conv_wrw_kernel(WrwArgs a)
         }
 }
 
+template <int MB, int NB>
+__global__ __launch_bounds__(256) void conv_wrw_kernel(WrwArgs a) { conv_wrw_body<MB, NB>(a, blockIdx.x, blockIdx.y); }
+
 struct WrwReduceArgs {
     const float* partial; int splits, nslice, Ca, Cb;    // partial [splits][slices][Ca][Cb]
     const float* xscale; const float* gscale;
@@ -838,13 +861,13 @@ struct WrwReduceArgs {
     signed char r[kMaxTaps], s[kMaxTaps], cnt[kMaxTaps], slice[kMaxTaps][4];
 };
 
-__global__ __launch_bounds__(256) void conv_wrw_reduce_kernel(WrwReduceArgs a)
+__device__ __forceinline__ void conv_wrw_reduce_body(const WrwReduceArgs& a, const unsigned bid)
 {
     // four lanes per output float4: each takes every fourth range, a fixed two-step butterfly joins them (the order of the
     // additions is the same in every run) -- four times the loads in flight of one thread walking all the ranges
-    if ((int)blockIdx.x >= a.main_blocks) {
+    if ((int)bid >= a.main_blocks) {
         // bias gradient: one wave per 4 channels, a lane adds every 64th partial row, fixed butterfly
-        const int u = ((int)blockIdx.x - a.main_blocks) * 256 + threadIdx.x, cg = u >> 6, lane = u & 63;
+        const int u = ((int)bid - a.main_blocks) * 256 + threadIdx.x, cg = u >> 6, lane = u & 63;
         if (cg >= a.c4n) return;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         for (int b = lane; b < kAmaxBlocks; b += 64) v += *reinterpret_cast<const f32x4*>(a.colsum + (int64_t)b * 4 * a.c4n + 4 * cg);
@@ -858,7 +881,7 @@ __global__ __launch_bounds__(256) void conv_wrw_reduce_kernel(WrwReduceArgs a)
     const int64_t plane = (int64_t)a.Ca * a.Cb, per = (int64_t)a.nslice * plane, total4 = (int64_t)a.nout * plane >> 2;
     const float inv = a.coef / (a.xscale[0] * a.gscale[0]);
     const int part = threadIdx.x & 3;
-    for (int64_t e4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 2; e4 < total4; e4 += (int64_t)a.main_blocks * 64) {
+    for (int64_t e4 = ((int64_t)bid * 256 + threadIdx.x) >> 2; e4 < total4; e4 += (int64_t)a.main_blocks * 64) {
         const int64_t e = e4 * 4;
         const int o = e / plane; const int64_t w = e - o * plane;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -883,6 +906,42 @@ __global__ __launch_bounds__(256) void conv_wrw_reduce_kernel(WrwReduceArgs a)
         if (a.sb == 1 && ((uintptr_t)out & 15) == 0) *reinterpret_cast<f32x4*>(out) = v;
         else { out[0] = v[0]; out[a.sb] = v[1]; out[2 * a.sb] = v[2]; out[3 * a.sb] = v[3]; }
     }
+}
+
+__global__ __launch_bounds__(256) void conv_wrw_reduce_kernel(WrwReduceArgs a) { conv_wrw_reduce_body(a, blockIdx.x); }
+
+// ---- one layer's backward in two launches: data gradient and weight gradient side by side -----------------------------------------------
+// The critic's 128-channel layers at 8x8 and 16x16 give each gradient about one workgroup per CU (one wave per SIMD), and the two need
+// nothing from each other: both read only the output gradient's planes and saved tensors.  As four launches the second pair waits behind
+// the first; here ONE grid holds the workgroups of both (conv_weights_pair_kernel's idiom: the role is a range of the linear block index,
+// wave-uniform) and one launch finishes both.  Two <2, 2> workgroups (<= 84 + 64 registers, 64 KiB of LDS each) share a CU.  No
+// cross-workgroup waits, atomics or counters: every workgroup runs the body it runs in conv_f16x3_kernel<2, 2, KS> / conv_wrw_kernel<2, 2>
+// on the same operands and the reductions keep their order, so dx, dW and db have the bits of the four launches.
+//   blocks [0, conv_blocks):  the data gradient's 3-d grid (gx, gy, ksplit), x fastest.  Its workgroups are the longer ones (9-36
+//                             iterations against the weight gradient's 4-20 chunks) and go first: measured against the other order at
+//                             batch 128, 37.3 / 77.7 / 50.5 / 19.2 us against 38.4 / 83.3 / 53.0 / 19.2 (profiles/conv_pair_shapes.txt)
+//   blocks [wrw_off, ...):    the weight gradient's (split, tile) as dim3(splits, tiles) linearises; wrw_off = conv_blocks rounded up to a
+//                             multiple of 8 (the blocks between return at once), so a pixel range keeps its residue mod 8, i.e. the
+//                             workgroups that read one range still share an XCD as wrw_splits means them to.
+template <bool KS>
+__global__ __launch_bounds__(256) void conv_bwd_pair_kernel(ConvArgs d, WrwArgs w, int conv_blocks, int wrw_off, int wrw_splits, int gx, int gy)
+{
+    const int b = blockIdx.x;
+    if (b < conv_blocks) {
+        const int t = b / gx, z = t / gy;
+        conv_f16x3_body<2, 2, KS>(d, (unsigned)(b - t * gx), (unsigned)(t - z * gy), (unsigned)z);
+    } else if (b >= wrw_off) {
+        const int e = b - wrw_off, tile = e / wrw_splits;
+        conv_wrw_body<2, 2>(w, (unsigned)(e - tile * wrw_splits), (unsigned)tile);
+    }
+}
+
+// blocks [0, wrw_blocks): conv_wrw_reduce_kernel's (main and bias-gradient blocks); the rest: conv_ksplit_reduce_kernel's
+__global__ __launch_bounds__(256) void conv_pair_reduce_kernel(WrwReduceArgs r, KsplitReduceArgs k, int wrw_blocks)
+{
+    if ((int)blockIdx.x < wrw_blocks) conv_wrw_reduce_body(r, blockIdx.x);
+    else conv_ksplit_reduce_body(k.partial, k.ksplit, k.n4, k.cout, k.xscale, k.wscale, k.bias, k.relu, k.y,
+                                 blockIdx.x - wrw_blocks, gridDim.x - wrw_blocks);
 }
 
 // ---- weight and bias gradient of a convolution with a handful of INPUT channels (round 5) ---------------------------------------------
@@ -1325,14 +1384,21 @@ size_t wc_conv_workspace_bytes(const wc_conv_geom* g)
     return k > 1 ? (size_t)k * g->N * g->Hout * g->Wout * g->Cout * 4 : 0;
 }
 
-int wc_conv_f16x3(const void* xhi, const void* xlo, const float* xscale, const void* wimage, const float* wscale,
-                  const float* bias, const void* zero_line, const wc_conv_geom* g, int relu, float* y,
-                  void* ws, size_t ws_bytes, wc_stream_t stream)
+// the 256-point tile <4, NB>: when it still gives every CU a workgroup
+static bool conv_big_tile(const wc_conv_geom* g, int ksplit)
 {
-    hipStream_t st = (hipStream_t)stream;
+    const int64_t M = (int64_t)g->N * g->H * g->W;
+    const bool wide = (g->Cout % 256) == 0;
+    const int64_t wgs_big = (M / 256) * g->nphase * (g->Cout / (wide ? 256 : 128));
+    return ksplit == 1 && (M % 256) == 0 && wgs_big >= 256;
+}
+
+// argument checks and the kernel's argument block of wc_conv_f16x3 (shared with wc_conv_bwd_pair_f16x3)
+static int conv_prepare(ConvArgs& a, const void* xhi, const void* xlo, const float* xscale, const void* wimage, const float* wscale,
+                        const float* bias, const void* zero_line, const wc_conv_geom* g, int relu, float* y, void* ws, size_t ws_bytes)
+{
     if (!xhi || !xlo || !xscale || !wimage || !wscale || !zero_line || !g || !y) return WC_ERR_ARG;
     if (!wc_conv_supported(g)) return WC_ERR_SHAPE;
-    ConvArgs a;
     a.xhi = (const _Float16*)xhi; a.xlo = (const _Float16*)xlo; a.zero = (const _Float16*)zero_line;
     a.wimg = (const char*)wimage; a.xscale = xscale; a.wscale = wscale; a.bias = bias; a.y = y;
     a.N = g->N; a.H = g->H; a.W = g->W; a.Hin = g->Hin; a.Win = g->Win; a.Cin = g->Cin; a.Cout = g->Cout;
@@ -1346,13 +1412,21 @@ int wc_conv_f16x3(const void* xhi, const void* xlo, const float* xscale, const v
         a.offy[p] = g->off_y[p]; a.offx[p] = g->off_x[p];
         for (int t = 0; t < kMaxTaps; ++t) { a.dy[p][t] = g->dy[p][t]; a.dx[p][t] = g->dx[p][t]; }
     }
-    const int64_t M = (int64_t)g->N * g->H * g->W;
+    return WC_OK;
+}
+
+int wc_conv_f16x3(const void* xhi, const void* xlo, const float* xscale, const void* wimage, const float* wscale,
+                  const float* bias, const void* zero_line, const wc_conv_geom* g, int relu, float* y,
+                  void* ws, size_t ws_bytes, wc_stream_t stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    ConvArgs a;
+    const int rc = conv_prepare(a, xhi, xlo, xscale, wimage, wscale, bias, zero_line, g, relu, y, ws, ws_bytes);
+    if (rc != WC_OK) return rc;
     const bool wide = (g->Cout % 256) == 0;
-    // the larger pixel tile when it still gives every CU a workgroup
-    const int64_t wgs_big = (M / 256) * g->nphase * (g->Cout / (wide ? 256 : 128));
     hipError_t e;
     if (g->Cout % 128)                                      e = a.ksplit > 1 ? launch_conv<2, 1, true>(a, st) : launch_conv<2, 1>(a, st);
-    else if (a.ksplit == 1 && (M % 256) == 0 && wgs_big >= 256) e = wide ? launch_conv<4, 4>(a, st) : launch_conv<4, 2>(a, st);
+    else if (conv_big_tile(g, a.ksplit))                    e = wide ? launch_conv<4, 4>(a, st) : launch_conv<4, 2>(a, st);
     else if (a.ksplit > 1)                                  e = wide ? launch_conv<2, 4, true>(a, st) : launch_conv<2, 2, true>(a, st);
     else                                                    e = wide ? launch_conv<2, 4>(a, st) : launch_conv<2, 2>(a, st);
     if (e != hipSuccess) return (int)e;
@@ -1499,15 +1573,20 @@ int wc_conv_wrw_f16x3(const void* xhi, const void* xlo, const float* xscale, con
                                   nullptr, nullptr, ws, ws_bytes, stream);
 }
 
-int wc_conv_wrw_bias_f16x3(const void* xhi, const void* xlo, const float* xscale, const void* ghi, const void* glo, const float* gscale,
-                           const void* zero_line, const wc_conv_geom* g, float* dw, int64_t stride_k, int64_t stride_n,
-                           int64_t stride_r, int64_t stride_s, const float* colsum_partials, float* db,
-                           void* ws, size_t ws_bytes, wc_stream_t stream)
+// argument checks and both kernels' argument blocks of wc_conv_wrw_bias_f16x3 (shared with wc_conv_bwd_pair_f16x3)
+struct WrwPlan { WrwArgs a; WrwReduceArgs r; int T, splits, tiles, extra; };
+
+static int wrw_prepare(WrwPlan& p, const void* xhi, const void* xlo, const float* xscale, const void* ghi, const void* glo, const float* gscale,
+                       const void* zero_line, const wc_conv_geom* g, float* dw, int64_t stride_k, int64_t stride_n,
+                       int64_t stride_r, int64_t stride_s, const float* colsum_partials, float* db, void* ws, size_t ws_bytes)
 {
-    hipStream_t st = (hipStream_t)stream;
     if (!xhi || !xlo || !xscale || !ghi || !glo || !gscale || !zero_line || !g || !dw || !ws) return WC_ERR_NULL;
     if (!wc_conv_supported(g) || (g->Cin & 63) || g->W < 2 || g->H * g->W < 2) return WC_ERR_SHAPE;
     if (ws_bytes < wc_conv_wrw_workspace_bytes(g)) return WC_ERR_WORKSPACE;
+    if ((colsum_partials == nullptr) != (db == nullptr)) return WC_ERR_NULL;
+    if (db && ((g->Cout & 3) || 256 % (g->Cout >> 2) != 0)) return WC_ERR_SHAPE;
+    WrwArgs& a = p.a;
+    WrwReduceArgs& r = p.r;
     int T;
     int splits = wrw_splits(g, &T);
     const int64_t M = (int64_t)g->N * g->H * g->W;
@@ -1517,28 +1596,26 @@ int wc_conv_wrw_bias_f16x3(const void* xhi, const void* xlo, const float* xscale
     WrwOperand X, G;
     X.hi = (const _Float16*)xhi; X.lo = (const _Float16*)xlo; X.Hp = g->Hin; X.Wp = g->Win; X.C = g->Cin; X.stride = g->in_stride;
     G.hi = (const _Float16*)ghi; G.lo = (const _Float16*)glo; G.Hp = g->Hout; G.Wp = g->Wout; G.C = g->Cout; G.stride = g->out_stride;
-    WrwReduceArgs r;
     r.nout = 0; r.coef = g->wcoef;
-    for (int p = 0; p < kMaxPhase; ++p)
+    for (int ph = 0; ph < kMaxPhase; ++ph)
         for (int t = 0; t < kMaxTaps; ++t) {
-            X.dy[p][t] = g->dy[p][t]; X.dx[p][t] = g->dx[p][t];
-            G.dy[p][t] = g->off_y[p]; G.dx[p][t] = g->off_x[p];
-            if (p >= g->nphase || t >= g->ntaps) continue;
-            if (g->nsrc[p][t] < 1 || g->nsrc[p][t] > 4) return WC_ERR_ARG;
-            for (int m = 0; m < g->nsrc[p][t]; ++m) {           // source tap -> the slices built from it
+            X.dy[ph][t] = g->dy[ph][t]; X.dx[ph][t] = g->dx[ph][t];
+            G.dy[ph][t] = g->off_y[ph]; G.dx[ph][t] = g->off_x[ph];
+            if (ph >= g->nphase || t >= g->ntaps) continue;
+            if (g->nsrc[ph][t] < 1 || g->nsrc[ph][t] > 4) return WC_ERR_ARG;
+            for (int m = 0; m < g->nsrc[ph][t]; ++m) {          // source tap -> the slices built from it
                 int o = 0;
-                while (o < r.nout && (r.r[o] != g->wr[p][t][m] || r.s[o] != g->ws[p][t][m])) ++o;
+                while (o < r.nout && (r.r[o] != g->wr[ph][t][m] || r.s[o] != g->ws[ph][t][m])) ++o;
                 if (o == r.nout) {
                     if (r.nout == kMaxTaps) return WC_ERR_ARG;
-                    r.r[o] = g->wr[p][t][m]; r.s[o] = g->ws[p][t][m]; r.cnt[o] = 0; ++r.nout;
+                    r.r[o] = g->wr[ph][t][m]; r.s[o] = g->ws[ph][t][m]; r.cnt[o] = 0; ++r.nout;
                 }
                 if (r.cnt[o] == 4) return WC_ERR_ARG;
-                r.slice[o][r.cnt[o]++] = (signed char)(p * g->ntaps + t);
+                r.slice[o][r.cnt[o]++] = (signed char)(ph * g->ntaps + t);
             }
         }
     // the lanes of a result tile run along its columns: put the weight's contiguous channel axis there
     const bool x_cols = stride_k == 1;
-    WrwArgs a;
     a.A = x_cols ? G : X; a.B = x_cols ? X : G;
     a.zero = (const _Float16*)zero_line; a.partial = (float*)ws;
     a.N = g->N; a.H = g->H; a.W = g->W; a.ntaps = g->ntaps; a.nphase = g->nphase;
@@ -1546,7 +1623,29 @@ int wc_conv_wrw_bias_f16x3(const void* xhi, const void* xlo, const float* xscale
     magic_u31((unsigned)g->W, &a.magW, &a.shW);
     a.nchunks = nchunks; a.cps = (nchunks + splits - 1) / splits;
     splits = (nchunks + a.cps - 1) / a.cps;         // no empty ranges
-    dim3 grid((unsigned)splits, (unsigned)tiles);
+    r.partial = (const float*)ws; r.splits = splits; r.nslice = nslice; r.Ca = a.A.C; r.Cb = a.B.C;
+    r.xscale = xscale; r.gscale = gscale; r.dw = dw;
+    r.sa = x_cols ? stride_n : stride_k; r.sb = x_cols ? stride_k : stride_n; r.sr = stride_r; r.ss = stride_s;
+    r.colsum = colsum_partials; r.db = db; r.c4n = db ? g->Cout >> 2 : 0;
+    r.main_blocks = grid_for((int64_t)r.nout * g->Cin * g->Cout);
+    p.T = T; p.splits = splits; p.tiles = tiles; p.extra = db ? (r.c4n * 64 + 255) / 256 : 0;
+    return WC_OK;
+}
+
+int wc_conv_wrw_bias_f16x3(const void* xhi, const void* xlo, const float* xscale, const void* ghi, const void* glo, const float* gscale,
+                           const void* zero_line, const wc_conv_geom* g, float* dw, int64_t stride_k, int64_t stride_n,
+                           int64_t stride_r, int64_t stride_s, const float* colsum_partials, float* db,
+                           void* ws, size_t ws_bytes, wc_stream_t stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    WrwPlan p;
+    const int rc = wrw_prepare(p, xhi, xlo, xscale, ghi, glo, gscale, zero_line, g, dw, stride_k, stride_n, stride_r, stride_s,
+                               colsum_partials, db, ws, ws_bytes);
+    if (rc != WC_OK) return rc;
+    const WrwArgs& a = p.a;
+    const WrwReduceArgs& r = p.r;
+    const int T = p.T;
+    dim3 grid((unsigned)p.splits, (unsigned)p.tiles);
     hipError_t e = hipSuccess;
     if (T == 256) {
         constexpr int LDS = 2 * (2 * 4 * 4 * 1024 + 2 * 4 * 4 * 1024);
@@ -1564,15 +1663,79 @@ int wc_conv_wrw_bias_f16x3(const void* xhi, const void* xlo, const float* xscale
         if (e != hipSuccess) return (int)e;
         hipLaunchKernelGGL((conv_wrw_kernel<2, 2>), grid, dim3(256), LDS, st, a);
     }
-    r.partial = (const float*)ws; r.splits = splits; r.nslice = nslice; r.Ca = a.A.C; r.Cb = a.B.C;
-    r.xscale = xscale; r.gscale = gscale; r.dw = dw;
-    r.sa = x_cols ? stride_n : stride_k; r.sb = x_cols ? stride_k : stride_n; r.sr = stride_r; r.ss = stride_s;
-    if ((colsum_partials == nullptr) != (db == nullptr)) return WC_ERR_NULL;
-    if (db && ((g->Cout & 3) || 256 % (g->Cout >> 2) != 0)) return WC_ERR_SHAPE;
-    r.colsum = colsum_partials; r.db = db; r.c4n = db ? g->Cout >> 2 : 0;
-    r.main_blocks = grid_for((int64_t)r.nout * g->Cin * g->Cout);
-    const int extra = db ? (r.c4n * 64 + 255) / 256 : 0;
-    hipLaunchKernelGGL(conv_wrw_reduce_kernel, dim3(r.main_blocks + extra), dim3(256), 0, st, r);
+    hipLaunchKernelGGL(conv_wrw_reduce_kernel, dim3(r.main_blocks + p.extra), dim3(256), 0, st, r);
+    return (int)hipGetLastError();
+}
+
+// ---- data gradient + weight gradient of one layer in two launches (conv_bwd_pair_kernel, conv_pair_reduce_kernel) -------------------------
+// gd = the data-gradient geometry (what wc_conv_f16x3 is given for dx), gf = the forward geometry (what wc_conv_wrw_bias_f16x3 is given).
+int wc_conv_bwd_pair_supported(const wc_conv_geom* gd, const wc_conv_geom* gf)
+{
+    if (!gd || !gf || !wc_conv_supported(gd) || !wc_conv_supported(gf) || (gf->Cin & 63) || gf->H * gf->W < 2) return 0;
+    // one layer: the data gradient reads the planes the weight gradient takes as gy, and writes an x-shaped tensor
+    if (gd->N != gf->N || gd->Cin != gf->Cout || gd->Cout != gf->Cin) return 0;
+    if (gd->Hin != gf->Hout || gd->Win != gf->Wout || gd->Hout != gf->Hin || gd->Wout != gf->Win) return 0;
+    // the critic's kinds -- 'same', 'down', 'down3': a dense forward whose data gradient reads gy at stride 1 (the up-sampling layers of
+    // the generator, a phase forward with a strided data gradient, stay on the four launches: not costed)
+    if (gf->nphase != 1 || gd->in_stride != 1) return 0;
+    // the data gradient on <2, 2, KS>: 128-wide output tiles, not the 256-point tile
+    if ((gd->Cout % 128) != 0 || (gd->Cout % 256) == 0 || conv_big_tile(gd, conv_ksplit(gd))) return 0;
+    int tile;
+    (void)wrw_splits(gf, &tile);
+    return tile == 128 ? 1 : 0;
+}
+
+size_t wc_conv_bwd_pair_workspace_bytes(const wc_conv_geom* gd, const wc_conv_geom* gf)
+{
+    if (!gd || !gf) return 0;
+    return wc_conv_workspace_bytes(gd) + wc_conv_wrw_workspace_bytes(gf);
+}
+
+int wc_conv_bwd_pair_f16x3(const void* ghi, const void* glo, const float* gscale, const void* wimage, const float* wscale,
+                           const void* zero_line, const wc_conv_geom* gd, float* dx, void* ws_dx, size_t ws_dx_bytes,
+                           const void* xhi, const void* xlo, const float* xscale, const wc_conv_geom* gf, float* dw,
+                           int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
+                           const float* colsum_partials, float* db, void* ws_dw, size_t ws_dw_bytes, wc_stream_t stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    ConvArgs d;
+    int rc = conv_prepare(d, ghi, glo, gscale, wimage, wscale, nullptr, zero_line, gd, 0, dx, ws_dx, ws_dx_bytes);
+    if (rc != WC_OK) return rc;
+    WrwPlan p;
+    rc = wrw_prepare(p, xhi, xlo, xscale, ghi, glo, gscale, zero_line, gf, dw, stride_k, stride_n, stride_r, stride_s,
+                     colsum_partials, db, ws_dw, ws_dw_bytes);
+    if (rc != WC_OK) return rc;
+    if (!wc_conv_bwd_pair_supported(gd, gf) || p.T != 128) return WC_ERR_SHAPE;
+    constexpr int LDS = 2 * (2 * 2 * 4 * 1024 + 2 * 2 * 4 * 1024);
+    const int64_t M = (int64_t)gd->N * gd->H * gd->W;
+    const int gx = (int)(M / 128), gy = gd->nphase * (gd->Cout / 128);          // launch_conv<2, 2>'s grid
+    const int64_t conv_blocks = (int64_t)gx * gy * d.ksplit, wrw_off = (conv_blocks + 7) & ~(int64_t)7;
+    const int64_t blocks = wrw_off + (int64_t)p.splits * p.tiles;
+    if (blocks > 0x7fffffff) return WC_ERR_SHAPE;
+    hipError_t e;
+    if (d.ksplit > 1) {
+        e = wc_set_max_lds(reinterpret_cast<const void*>(conv_bwd_pair_kernel<true>), LDS);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL((conv_bwd_pair_kernel<true>), dim3((unsigned)blocks), dim3(256), LDS, st, d, p.a,
+                           (int)conv_blocks, (int)wrw_off, p.splits, gx, gy);
+    } else {
+        e = wc_set_max_lds(reinterpret_cast<const void*>(conv_bwd_pair_kernel<false>), LDS);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL((conv_bwd_pair_kernel<false>), dim3((unsigned)blocks), dim3(256), LDS, st, d, p.a,
+                           (int)conv_blocks, (int)wrw_off, p.splits, gx, gy);
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    const int reduce_blocks = p.r.main_blocks + p.extra;
+    if (d.ksplit > 1) {
+        KsplitReduceArgs k;
+        k.n4 = (int64_t)gd->N * gd->Hout * gd->Wout * gd->Cout / 4;
+        k.partial = (const float*)ws_dx; k.ksplit = d.ksplit; k.cout = gd->Cout;
+        k.xscale = gscale; k.wscale = wscale; k.bias = nullptr; k.relu = 0; k.y = dx;
+        hipLaunchKernelGGL(conv_pair_reduce_kernel, dim3(reduce_blocks + grid_for(k.n4)), dim3(256), 0, st, p.r, k, reduce_blocks);
+    } else {
+        hipLaunchKernelGGL(conv_wrw_reduce_kernel, dim3(reduce_blocks), dim3(256), 0, st, p.r);
+    }
     return (int)hipGetLastError();
 }
 
