@@ -637,6 +637,26 @@ int wc_conv_f16x3(const void* xhi, const void* xlo, const float* xscale, const v
                   const float* bias, const void* zero_line, const wc_conv_geom* g, int relu, float* y,
                   void* ws, size_t ws_bytes, wc_stream_t stream);
 
+/* The passes between the critic's convolutions (discriminator.py:41-54: relu -> conv -> relu -> conv (-> pool), + shortcut), in the
+ * launches that are there anyway.  These three entries are new; WC_CORE_API keeps its list and WC_ABI_VERSION, which covers that core,
+ * its value.  (The same change is NOT additive for two extension entries further down: wc_conv_split_masked_f32 and
+ * wc_conv_split_hist_masked_f32 took `colsum_partials, C` in front of their trailing arguments.  A caller built against their old
+ * signatures has to be rebuilt; the binding table of _lib.py refuses a library without the new symbols below, old or new.)
+ * wc_conv_res_f16x3: y = (conv(x, w) + bias) + res, res of y's shape -- the block's `h + s` in the finish of the convolution whose tap
+ *   loop is shared over workgroups (wc_conv_res_supported: wc_conv_workspace_bytes(g) > 0 and Cout a multiple of 128); the bits of
+ *   wc_conv_f16x3 followed by an elementwise fp32 add.  Other geometries: WC_ERR_SHAPE, the caller adds.  ws as in wc_conv_f16x3.
+ * wc_conv_block_dx_f32: the gradient of a block's input from the first convolution's data gradient dx1, the block input x (the ReLU's
+ *   mask: x <= 0 gives +0, a NaN lets the gradient through, as aten::threshold_backward) and the other branch, NHWC, C % 4 == 0:
+ *     down == 0:  out = mask(dx1) + other,                          other [N,H,W,C]: the block's output gradient (identity shortcut)
+ *     down != 0:  out = mask(dx1) + 0.25 * other[n][y/2][x/2][c],   other [N,H/2,W/2,C]: the gradient in front of the 2x2 average pooling
+ *   (0.25 * other rounded on its own, then one add: the bits of the three elementwise passes it replaces).  out must not alias an input. */
+int wc_conv_res_supported(const wc_conv_geom* g);
+int wc_conv_res_f16x3(const void* xhi, const void* xlo, const float* xscale, const void* wimage, const float* wscale,
+                      const float* bias, const float* res, const void* zero_line, const wc_conv_geom* g, float* y,
+                      void* ws, size_t ws_bytes, wc_stream_t stream);
+int wc_conv_block_dx_f32(const float* dx1, const float* x, const float* other, int64_t N, int64_t H, int64_t W, int C, int down,
+                         float* out, wc_stream_t stream);
+
 /* Weight gradient of the same convolution: dW(k, n, r, s) = sum over the grid of x[input pixel][k] * gy[output pixel][n]
  * for the FORWARD geometry `g` (x and gy as split planes; Cin and Cout multiples of 64 -- 64 x 64 tiles when either is no multiple
  * of 128), written to
@@ -835,11 +855,15 @@ int    wc_bwd_factor_renorm_f64(const double* R, const double* gsum, const doubl
 /* The operand split of a tangent: planes of t[i] * (a[i] > 0 ? 1 : slope), a = the primal pre-activation (fp32, t's shape), 0 <= slope <= 1
  * (0: the ResNet critic's ReLU; the DC critic's LeakyReLU is 0.3).  (hi, lo, scale), the scale rule, the `hist` record, `bootstrap` and the
  * gated second pass are those of wc_conv_split_f32 / wc_conv_split_hist_f32: the planes and the scale are bit for bit what those entries
- * give for the premultiplied fp32 tensor, without that tensor.  n % 4 == 0. */
+ * give for the premultiplied fp32 tensor, without that tensor.  n % 4 == 0.
+ * colsum_partials / C (nullable) as in wc_conv_split_colsum_f32 / wc_conv_split_hist_f32: the 512 partial rows of the column sums of the
+ * MASKED values, bit for bit the rows those entries leave for the premultiplied tensor -- a convolution's output gradient behind a ReLU
+ * (t = the data gradient of the layer behind it, a = this layer's output) needs no masked fp32 copy for its split or its bias gradient.
+ * SIGNATURE CHANGE (WC_ABI_VERSION stays 8, it versions WC_CORE_API): both entries had no `colsum_partials, C` before. */
 int wc_conv_split_masked_f32(const float* t, const float* a, int64_t n, float slope, void* hi, void* lo, float* scale, void* amax_scratch,
-                             wc_stream_t stream);
-int wc_conv_split_hist_masked_f32(const float* t, const float* a, int64_t n, float slope, void* hi, void* lo, float* scale, float* hist,
-                                  int bootstrap, wc_stream_t stream);
+                             float* colsum_partials /*nullable*/, int C, wc_stream_t stream);
+int wc_conv_split_hist_masked_f32(const float* t, const float* a, int64_t n, float slope, void* hi, void* lo, float* scale,
+                                  float* colsum_partials /*nullable*/, int C, float* hist, int bootstrap, wc_stream_t stream);
 
 /* x_hat[n] = eps[n] real[n] + (1 - eps[n]) fake[n] for N samples of L floats, eps [N] on the device (formed in float64, rounded once). */
 int wc_gp_interp_f32(const float* real, const float* fake, const float* eps, int64_t N, int64_t L, float* x_hat, wc_stream_t stream);

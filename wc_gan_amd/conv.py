@@ -111,7 +111,7 @@ def supported(x, w, kind):
 class _Plan:
     """Everything about a call that depends on the shapes only, built once: the two geometries, the weight axes, the
     support verdict and the workspace sizes (the per-call host work is what is left: a few allocations and launches)."""
-    __slots__ = ('ok', 'fwd', 'bwd', 'fwd_ws', 'bwd_ws', 'wrw_ws', 'fwd_ptr', 'bwd_ptr', 'pair')
+    __slots__ = ('ok', 'fwd', 'bwd', 'fwd_ws', 'bwd_ws', 'wrw_ws', 'fwd_ptr', 'bwd_ptr', 'pair', 'res')
 
     def __init__(self, kind, N, H, W, wshape):
         class _W:                                   # shape-only stand-in for the weight
@@ -126,6 +126,8 @@ class _Plan:
         self.wrw_ws = lib.wc_conv_wrw_workspace_bytes(self.fwd_ptr) if self.ok else 0
         # data gradient and weight gradient in one grid (wc_conv_bwd_pair_f16x3): the critic's 128-channel layers
         self.pair = self.ok and bool(lib.wc_conv_bwd_pair_supported(self.bwd_ptr, self.fwd_ptr))
+        # a residual operand in the forward's finish (wc_conv_res_f16x3): the layers whose tap loop is shared over workgroups
+        self.res = self.ok and bool(lib.wc_conv_res_supported(self.fwd_ptr))
 
 
 _plans = {}
@@ -243,26 +245,45 @@ def _split_planes_leaky(lib, x, slope, colsum, site, role):
     return (hi, lo, scale, part) if colsum else (hi, lo, scale)
 
 
-def split_planes_masked(t, a, slope=0.0, site=None, role='t'):
+def split_planes_masked(t, a, slope=0.0, site=None, role='t', colsum=False):
     """(hi, lo, scale) of t * (a > 0 ? 1 : slope) -- a tangent behind a ReLU (slope 0) or LeakyReLU whose primal pre-activation was `a` --
     in the launches of split_planes and with its bits on the premultiplied tensor (wc_conv_split[_hist]_masked_f32, csrc/wc_gp.hip).
-    site / role as in split_planes; role 't' takes the gated second pass."""
+    site / role as in split_planes; roles 't' and 'g' take the gated second pass.  colsum: as in split_planes, the partial rows of the
+    column sums of the masked values as a 4th element (the critic block's backward: t = conv2's data gradient, a = conv1's output)."""
     if not (t.is_contiguous() and a.is_contiguous() and t.shape == a.shape and t.dtype == a.dtype == torch.float32):
         raise ValueError("split_planes_masked: dense fp32 tensors of one shape")
     lib = _lib.load()
     both = torch.empty((2,) + tuple(t.shape), dtype=torch.float16, device=t.device)
     hi, lo = both[0], both[1]
     scale = torch.empty(1 + 512, dtype=torch.float32, device=t.device)
+    C = t.shape[-1]
+    part = torch.empty((512, C), dtype=torch.float32, device=t.device) if colsum else None
     h = _site_hist(site, role, t.device) if (SPLIT_HIST and site is not None) else None
     if h is not None:
-        _lib.check(lib.wc_conv_split_hist_masked_f32(_ptr(t), _ptr(a), t.numel(), float(slope), _ptr(hi), _ptr(lo), _ptr(scale), _ptr(h[0]),
+        _lib.check(lib.wc_conv_split_hist_masked_f32(_ptr(t), _ptr(a), t.numel(), float(slope), _ptr(hi), _ptr(lo), _ptr(scale),
+                                                     _ptr(part), C if colsum else 0, _ptr(h[0]),
                                                      (0 if h[1] else 1) | (0 if _guarded(role) else 2), _stream()),
                    "wc_conv_split_hist_masked_f32")
         h[1] = True
     else:
         _lib.check(lib.wc_conv_split_masked_f32(_ptr(t), _ptr(a), t.numel(), float(slope), _ptr(hi), _ptr(lo), _ptr(scale),
-                                                scale.data_ptr() + 4, _stream()), "wc_conv_split_masked_f32")
-    return hi, lo, scale
+                                                scale.data_ptr() + 4, _ptr(part), C if colsum else 0, _stream()), "wc_conv_split_masked_f32")
+    return (hi, lo, scale, part) if colsum else (hi, lo, scale)
+
+
+def block_input_gradient(dx1, x, other, down):
+    """(x > 0 ? dx1 : 0) + other, or + 0.25 * other[n, y/2, x/2, c] when `down` (other at half resolution: the gradient in front of the
+    block's 2x2 average pooling) -- threshold_backward, avg_pool2d's backward and the add that joins a critic block's two branches in one
+    launch and with their bits (wc_conv_block_dx_f32).  NHWC fp32."""
+    N, H, W, C = dx1.shape
+    want = (N, H // 2, W // 2, C) if down else (N, H, W, C)
+    if not (dx1.is_contiguous() and x.is_contiguous() and other.is_contiguous() and x.shape == dx1.shape and tuple(other.shape) == want
+            and dx1.dtype == x.dtype == other.dtype == torch.float32):
+        raise ValueError("block_input_gradient: dense fp32 NHWC tensors, `other` of dx1's shape (at half resolution when down)")
+    out = torch.empty_like(dx1)
+    _lib.check(_lib.load().wc_conv_block_dx_f32(_ptr(dx1), _ptr(x), _ptr(other), N, H, W, C, 1 if down else 0, _ptr(out), _stream()),
+               "wc_conv_block_dx_f32")
+    return out
 
 
 def leaky_backward_(dx, x, slope):
@@ -321,7 +342,9 @@ def _cached_image(w, key, geom, k_axis, n_axis):
     return weight_image(w, geom, k_axis, n_axis)
 
 
-def run(planes, image, geom, bias=None, relu=False, nbytes=None):
+def run(planes, image, geom, bias=None, relu=False, nbytes=None, res=None):
+    """res: a tensor of the output's shape added to the result in the convolution's finish (wc_conv_res_f16x3: the geometries
+    wc_conv_res_supported takes, _Plan.res)"""
     hi, lo, xs = planes
     img, ws = image
     lib = _lib.load()
@@ -329,6 +352,13 @@ def run(planes, image, geom, bias=None, relu=False, nbytes=None):
     if nbytes is None:
         nbytes = lib.wc_conv_workspace_bytes(ctypes.addressof(geom))
     work = torch.empty(nbytes, dtype=torch.uint8, device=hi.device) if nbytes else None
+    if res is not None:
+        if relu or not (res.is_contiguous() and res.shape == y.shape and res.dtype == torch.float32 and res.device == y.device):
+            raise ValueError("run: the residual is a dense fp32 tensor of the output's shape (and there is no ReLU behind it)")
+        _lib.check(lib.wc_conv_res_f16x3(_ptr(hi), _ptr(lo), _ptr(xs), _ptr(img), _ptr(ws), _ptr(bias) if bias is not None else None,
+                                         _ptr(res), _ptr(_zero_line(hi.device)), ctypes.addressof(geom), _ptr(y),
+                                         _ptr(work), nbytes, _stream()), "wc_conv_res_f16x3")
+        return y
     _lib.check(lib.wc_conv_f16x3(_ptr(hi), _ptr(lo), _ptr(xs), _ptr(img), _ptr(ws), _ptr(bias) if bias is not None else None,
                                  _ptr(_zero_line(hi.device)), ctypes.addressof(geom), 1 if relu else 0, _ptr(y),
                                  _ptr(work), nbytes, _stream()), "wc_conv_f16x3")
@@ -418,7 +448,7 @@ def takes_planes(shape, wshape, kind):
 
 class _FastConv(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, bias, kind, plan, relu_input=False, handed=None, site=None, leaky=None):
+    def forward(ctx, x, w, bias, kind, plan, relu_input=False, handed=None, site=None, leaky=None, residual=None):
         gf, kf, nf = plan.fwd
         # handed: x is a K3 handle and these are its planes (already ReLU'd and split by K3's epilogue: no pass here)
         # relu_input: the layer is conv(relu(x)); the ReLU happens in the split
@@ -430,7 +460,13 @@ class _FastConv(torch.autograd.Function):
             img, ctx.bwd_image = weight_image_pair(w, plan.fwd, plan.bwd)
         else:
             img, ctx.bwd_image = weight_image(w, gf, kf, nf), None
-        y = run(planes, img, gf, bias, nbytes=plan.fwd_ws)
+        # residual: y = conv(x) + residual, in the convolution's finish where it has one that takes it (plan.res), else added here
+        if residual is not None and plan.res and FUSED_RESIDUAL:
+            y = run(planes, img, gf, bias, nbytes=plan.fwd_ws, res=residual.contiguous())
+        else:
+            y = run(planes, img, gf, bias, nbytes=plan.fwd_ws)
+            if residual is not None:
+                y = y + residual
         # the planes stand in for (relu of) x (same bytes) in the weight gradient; x itself only for the ReLU mask
         ctx.save_for_backward(w, *planes, *((x,) if (relu_input or leaky is not None) else ()))
         ctx.kind, ctx.has_bias, ctx.plan, ctx.relu_input = kind, bias is not None, plan, relu_input
@@ -468,7 +504,8 @@ class _FastConv(torch.autograd.Function):
                 dw = weight_gradient((xh, xl, xs), g_planes, gf, w, kf, nf, nbytes=plan.wrw_ws)
         if want_db and not fused_db:
             db = gy.sum((0, 1, 2))
-        return dx, dw, db, None, None, None, None, None, None
+        need = ctx.needs_input_grad
+        return dx, dw, db, None, None, None, None, None, None, (gy if len(need) > 9 and need[9] else None)
 
 
 _ones = {}
@@ -697,8 +734,183 @@ def narrow_out_wrw_supported(x, w):
     return bool(_lib.load().wc_conv_wrw_narrow_supported(N, H, W, w.shape[0], C, k))
 
 
-def fast_conv(x, w, bias=None, kind='same'):
-    """NHWC convolution (see the module docstring) -- raises if the shape is not one the kernel takes."""
+def fast_conv(x, w, bias=None, kind='same', residual=None):
+    """NHWC convolution (see the module docstring) -- raises if the shape is not one the kernel takes.
+    residual: a tensor of the output's shape; the result is conv(x) + residual with the bits of that sum, added in the convolution's
+    finish where the tap loop is shared over workgroups (wc_conv_res_f16x3), by an elementwise add behind the other geometries."""
     if not supported(x, w, kind):
         raise _lib.WcHipError(f"fast_conv: unsupported call {tuple(x.shape)} x {tuple(w.shape)} ({kind})")
-    return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w))
+    if residual is None:
+        return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w))
+    return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w), False, None, None, None, residual)
+
+
+# ---- the critic's residual block as one autograd node ------------------------------------------------------------------------------------
+# discriminator.ResBlockDown behind the first block, without a norm: y = conv2(relu(conv1(relu(x)))) [pooled] + (shortcut(pool(x)) | x).
+# As separate nodes the passes BETWEEN the convolutions were torch's: threshold_backward over conv2's data gradient (which conv1's
+# backward then read again to split it), threshold_backward + avg_pool2d_backward + add for the block input's gradient, and the block's
+# `h + s` over an output its convolution had just written.  Here the mask rides in the split (split_planes_masked), the input's gradient
+# is one launch (block_input_gradient) and the add one operand of conv2's finish (run(res=...)).  The convolutions, their sites' records
+# and roles, and the order of every sum are those of the separate nodes: same bits.  FUSED_BLOCK = False: the separate nodes (tests and
+# tools/critic_glue_bench.py compare the two in one process); the three FUSED_* flags below switch one part each, for that tool.
+FUSED_BLOCK = True
+FUSED_MASKED_SPLIT = True       # (a) conv2's data gradient is masked while conv1's backward splits it
+FUSED_RESIDUAL = True           # (b) h + s in conv2's finish
+FUSED_BLOCK_DX = True           # (c) the block input's gradient in one launch
+
+
+class _Shape:
+    def __init__(self, shape):
+        self.shape = tuple(shape)
+
+
+def critic_block_plans(xshape, w1shape, w2shape, wsshape, down):
+    """(plan of conv1, of conv2, of the shortcut | None) when the fused block takes these shapes, else None.  Shapes only: x NHWC,
+    the weights (Cout, Cin, k, k), wsshape None for the identity shortcut, down = the block halves the grid."""
+    if len(xshape) != 4 or len(w1shape) != 4 or len(w2shape) != 4:
+        return None
+    N, H, W, C = xshape
+    F1, F2 = w1shape[0], w2shape[0]
+    if tuple(w1shape[1:]) != (C, 3, 3) or tuple(w2shape[1:]) != (F1, 3, 3):
+        return None
+    if down and (H % 2 or W % 2):
+        return None
+    if wsshape is None:
+        if down or F2 != C:
+            return None
+    elif tuple(wsshape) != (F2, C, 1, 1):
+        return None
+    if not (_colsum_ok(F1) and _colsum_ok(F2)):          # the bias gradients ride on the splits: no masked fp32 tensor to sum
+        return None
+    out = (N, H // 2, W // 2) if down else (N, H, W)
+    p1 = _plan('same', _Shape(xshape), _Shape(w1shape))
+    p2 = _plan('down3' if down else 'same', _Shape((N, H, W, F1)), _Shape(w2shape))
+    ps = _plan('same', _Shape(out + (C,)), _Shape(wsshape)) if wsshape is not None else None
+    if not (p1 and p1.ok and p2 and p2.ok and (wsshape is None or (ps and ps.ok))):
+        return None
+    return p1, p2, ps
+
+
+def _images(w, plan, both):
+    """(forward image, data-gradient image | None): _FastConv.forward's choice"""
+    if both:
+        return weight_image_pair(w, plan.fwd, plan.bwd)
+    gf, kf, nf = plan.fwd
+    return weight_image(w, gf, kf, nf), None
+
+
+def _layer_gradients(g_planes, fused_db, x_planes, w, plan, bwd_image, need_dx, need_dw):
+    """The launches of _FastConv.backward behind the split of the output gradient -> (dx, dW, db | None); dx is the convolution's data
+    gradient as it comes (no activation's backward)."""
+    cs = g_planes[3] if fused_db else None
+    if need_dx and need_dw and bwd_image is not None and plan.pair:
+        return backward_pair(g_planes, bwd_image, x_planes, plan, w, colsum=cs)
+    dx = dw = db = None
+    if need_dx:
+        gb, kb, nb = plan.bwd
+        image = bwd_image if bwd_image is not None else weight_image(w, gb, kb, nb)
+        dx = run(g_planes[:3], image, gb, nbytes=plan.bwd_ws)
+    if need_dw:
+        gf, kf, nf = plan.fwd
+        if fused_db:
+            dw, db = weight_gradient(x_planes, g_planes, gf, w, kf, nf, nbytes=plan.wrw_ws, colsum=cs)
+        else:
+            dw = weight_gradient(x_planes, g_planes, gf, w, kf, nf, nbytes=plan.wrw_ws)
+    return dx, dw, db
+
+
+def _pool2(x):
+    return F.avg_pool2d(x.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1).contiguous()
+
+
+class _CriticBlock(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, ws, bs, sites, plans, down):
+        conv1, conv2, shortcut = sites
+        p1, p2, ps = plans
+        need = ctx.needs_input_grad
+        need_h = need[0] or need[1] or need[2]
+        x_pl = split_planes(x, relu=True, site=conv1, role='x')
+        img1, bimg1 = _images(w1, p1, need[0])
+        h = run(x_pl, img1, p1.fwd[0], b1, nbytes=p1.fwd_ws)
+        h_pl = split_planes(h, relu=True, site=conv2, role='x')
+        img2, bimg2 = _images(w2, p2, need_h)
+        s, s_pl, bimgs = x, (), None
+        if ws is not None:
+            s_pl = split_planes(_pool2(x) if down else x, site=shortcut, role='x')
+            imgs, bimgs = _images(ws, ps, need[0])
+            s = run(s_pl, imgs, ps.fwd[0], bs, nbytes=ps.fwd_ws)
+        if p2.res and FUSED_RESIDUAL:
+            y = run(h_pl, img2, p2.fwd[0], b2, nbytes=p2.fwd_ws, res=s)
+        else:
+            y = run(h_pl, img2, p2.fwd[0], b2, nbytes=p2.fwd_ws) + s
+        ctx.save_for_backward(x, h, w1, w2, *x_pl, *h_pl, *s_pl, *((ws,) if ws is not None else ()))
+        ctx.sites, ctx.plans, ctx.down = sites, plans, down
+        ctx.images = (bimg1, bimg2, bimgs)
+        ctx.has_bias = (b1 is not None, b2 is not None, bs is not None)
+        # h leaves only for whoever watches the block's second norm site: no gradient, and none made up for it in backward
+        # (autograd would otherwise hand backward a zero-filled tensor of h's shape: a pass over memory per block)
+        ctx.mark_non_differentiable(h)
+        ctx.set_materialize_grads(False)
+        return y, h
+
+    @staticmethod
+    def backward(ctx, g, _gh):
+        saved = ctx.saved_tensors
+        x, h, w1, w2 = saved[:4]
+        x_pl, h_pl = saved[4:7], saved[7:10]
+        conv1, conv2, shortcut = ctx.sites
+        p1, p2, ps = ctx.plans
+        bimg1, bimg2, bimgs = ctx.images
+        need = ctx.needs_input_grad
+        need_h = need[0] or need[1] or need[2]
+        if g is None:               # (gradients are not materialised: nothing reached y)
+            return (None,) * 10
+        g = g.contiguous()
+        dx = dw1 = db1 = dw2 = db2 = dws = dbs = dx1 = None
+
+        def bias_rides(has, need_b, need_w, C):
+            return has and need_b and need_w and _colsum_ok(C)
+
+        # conv2: its output gradient is the block's; its data gradient stays unmasked
+        fused2 = bias_rides(ctx.has_bias[1], need[4], need[3], g.shape[-1])
+        g2 = split_planes(g, colsum=fused2, site=conv2, role='g')
+        dh, dw2, db2 = _layer_gradients(g2, fused2, h_pl, w2, p2, bimg2, need_h, need[3])
+        if ctx.has_bias[1] and need[4] and not fused2:
+            db2 = g.sum((0, 1, 2))
+        # conv1: the ReLU between the two (mask: conv1's output h) happens while conv2's data gradient is split
+        if need_h:
+            fused1 = bias_rides(ctx.has_bias[0], need[2], need[1], h.shape[-1])
+            if FUSED_MASKED_SPLIT:
+                g1 = split_planes_masked(dh, h, site=conv1, role='g', colsum=fused1)
+            else:
+                g1 = split_planes(torch.ops.aten.threshold_backward(dh, h, 0), colsum=fused1, site=conv1, role='g')
+            dx1, dw1, db1 = _layer_gradients(g1, fused1, x_pl, w1, p1, bimg1, need[0], need[1])
+            if ctx.has_bias[0] and need[2] and not fused1:
+                db1 = torch.ops.aten.threshold_backward(dh, h, 0).sum((0, 1, 2))
+        # the shortcut, as its own node ran it
+        other = g
+        if ps is not None:
+            ws = saved[13]
+            fuseds = bias_rides(ctx.has_bias[2], need[6], need[5], g.shape[-1])
+            gs = split_planes(g, colsum=fuseds, site=shortcut, role='g')
+            other, dws, dbs = _layer_gradients(gs, fuseds, saved[10:13], ws, ps, bimgs, need[0], need[5])
+            if ctx.has_bias[2] and need[6] and not fuseds:
+                dbs = g.sum((0, 1, 2))
+        if need[0]:
+            if FUSED_BLOCK_DX:
+                dx = block_input_gradient(dx1, x, other, ctx.down)
+            else:
+                dx = torch.ops.aten.threshold_backward(dx1, x, 0)
+                if ctx.down:
+                    other = torch.ops.aten.avg_pool2d_backward(other.permute(0, 3, 1, 2), x.permute(0, 3, 1, 2), [2, 2], [2, 2], [0, 0],
+                                                               False, True, None).permute(0, 2, 3, 1)
+                dx = dx + other
+        return dx, dw1, db1, dw2, db2, dws, dbs, None, None, None
+
+
+def critic_block(x, w1, b1, w2, b2, ws, bs, sites, plans, down):
+    """One critic block behind the first (see above): x NHWC fp32 on the GPU, the three weights as their layers hand them out (ws / bs
+    None: identity shortcut), sites = the three layer objects (the shortcut's None with ws), plans from critic_block_plans.
+    -> (y, h): the block's output and, detached, conv1's output (the tensor the block's second norm site sees)."""
+    return _CriticBlock.apply(x, w1, b1, w2, b2, ws, bs, sites, plans, down)

@@ -255,8 +255,10 @@ struct KsplitReduceArgs {
 __device__ __forceinline__ void conv_ksplit_reduce_body(const float* __restrict__ partial, int ksplit, int64_t n4, int cout,
                                                         const float* __restrict__ xscale, const float* __restrict__ wscale,
                                                         const float* __restrict__ bias, int relu, float* __restrict__ y,
-                                                        const unsigned bid, const unsigned nblocks)
+                                                        const unsigned bid, const unsigned nblocks, const float* __restrict__ res = nullptr)
 {
+    // res (y's shape, nullable): the residual block's other branch, added to the finished value -- y = (acc * inv + bias) + res, the bits of
+    // the elementwise add that used to read y straight back (discriminator.py:41-54 `Add()([h, s])`)
     const float inv = 1.0f / (xscale[0] * wscale[0]);
     for (int64_t i = (int64_t)bid * 256 + threadIdx.x; i < n4; i += (int64_t)nblocks * 256) {
         f32x4 v = *reinterpret_cast<const f32x4*>(partial + 4 * i);
@@ -272,6 +274,11 @@ __device__ __forceinline__ void conv_ksplit_reduce_body(const float* __restrict_
         v = v * inv;
         if (bias) v += *reinterpret_cast<const f32x4*>(bias + (4 * i) % cout);
         if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+        if (res) {
+            const f32x4 r = *reinterpret_cast<const f32x4*>(res + 4 * i);
+            #pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = __fadd_rn(v[j], r[j]);        // (its own rounding: never contracted into the line above)
+        }
         *reinterpret_cast<f32x4*>(y + 4 * i) = v;
     }
 }
@@ -281,6 +288,15 @@ __global__ __launch_bounds__(256) void conv_ksplit_reduce_kernel(const float* __
                                                                  const float* __restrict__ bias, int relu, float* __restrict__ y)
 {
     conv_ksplit_reduce_body(partial, ksplit, n4, cout, xscale, wscale, bias, relu, y, blockIdx.x, gridDim.x);
+}
+
+// the same finish with the residual operand (wc_conv_res_f16x3); a kernel of its own, so that the one above keeps its code
+__global__ __launch_bounds__(256) void conv_ksplit_reduce_res_kernel(const float* __restrict__ partial, int ksplit, int64_t n4, int cout,
+                                                                     const float* __restrict__ xscale, const float* __restrict__ wscale,
+                                                                     const float* __restrict__ bias, const float* __restrict__ res,
+                                                                     float* __restrict__ y)
+{
+    conv_ksplit_reduce_body(partial, ksplit, n4, cout, xscale, wscale, bias, 0, y, blockIdx.x, gridDim.x, res);
 }
 
 // the activation in front of a split: relu 0 = none, 1 = ReLU, 2 = LeakyReLU (x > 0 ? x : slope * x, one fp32 multiply; Keras's
@@ -353,6 +369,41 @@ __global__ __launch_bounds__(256) void conv_leaky_bwd_kernel(float* __restrict__
         #pragma unroll
         for (int j = 0; j < 4; ++j) g[j] = v[j] > 0.f ? g[j] : slope * g[j];
         *reinterpret_cast<f32x4*>(dx + 4 * i) = g;
+    }
+}
+
+// The gradient of a critic block's input in one pass (discriminator.py:41-54: the block is conv(relu(x)) ... + shortcut(pool(x)) or + x):
+//     DOWN == false:  out = (x > 0 ? dx1 : 0) + g                              g = the block's output gradient (identity shortcut)
+//     DOWN == true:   out = (x > 0 ? dx1 : 0) + 0.25 * ds[n][y / 2][x / 2][c]   ds = the shortcut's data gradient at half resolution
+// i.e. threshold_backward, the 2x2 average pooling's backward and the add that joins them, with their bits: the masked-out value is +0,
+// a NaN in x lets the gradient through (x <= 0 is false), 0.25 * ds is rounded on its own and the sum once.  c4 = C / 4, W, H of dx1.
+template <bool DOWN>
+__global__ __launch_bounds__(256) void conv_block_dx_kernel(const float* __restrict__ dx1, const float* __restrict__ x,
+                                                            const float* __restrict__ other, int64_t n4, int c4, int W, int H,
+                                                            float* __restrict__ out)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const f32x4 d = *reinterpret_cast<const f32x4*>(dx1 + 4 * i);
+        const f32x4 a = *reinterpret_cast<const f32x4*>(x + 4 * i);
+        int64_t j = i;
+        if (DOWN) {
+            const int64_t pix = i / c4;
+            const int c = (int)(i - pix * c4);
+            const int64_t row = pix / W;
+            const int xx = (int)(pix - row * W);
+            const int64_t n = row / H;
+            const int yy = (int)(row - n * H);
+            j = ((n * (H >> 1) + (yy >> 1)) * (W >> 1) + (xx >> 1)) * c4 + c;
+        }
+        const f32x4 o = *reinterpret_cast<const f32x4*>(other + 4 * j);
+        f32x4 r;
+        #pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float m = a[k] <= 0.f ? 0.f : d[k];
+            // (the pooling's backward accumulates its one term onto +0: a -0 quarter leaves it as +0)
+            r[k] = __fadd_rn(m, DOWN ? __fadd_rn(0.f, __fmul_rn(0.25f, o[k])) : o[k]);
+        }
+        *reinterpret_cast<f32x4*>(out + 4 * i) = r;
     }
 }
 
@@ -1435,6 +1486,45 @@ int wc_conv_f16x3(const void* xhi, const void* xlo, const float* xscale, const v
         hipLaunchKernelGGL(conv_ksplit_reduce_kernel, dim3(grid_for(n4)), dim3(256), 0, st, (const float*)ws, a.ksplit, n4, g->Cout,
                            xscale, wscale, bias, relu, y);
     }
+    return (int)hipGetLastError();
+}
+
+// wc_conv_f16x3 with the residual operand in the k-split finish: only geometries whose tap loop is shared (wc_conv_workspace_bytes > 0)
+// and whose width is a multiple of 128 -- the critic's conv2 at 8x8 and 16->8; the tiles' direct epilogue (and with it every
+// conv_f16x3_kernel instantiation's code) is left as it is, its caller adds the residual itself.
+int wc_conv_res_supported(const wc_conv_geom* g)
+{
+    return g && wc_conv_supported(g) && (g->Cout % 128) == 0 && conv_ksplit(g) > 1;
+}
+
+int wc_conv_res_f16x3(const void* xhi, const void* xlo, const float* xscale, const void* wimage, const float* wscale,
+                      const float* bias, const float* res, const void* zero_line, const wc_conv_geom* g, float* y,
+                      void* ws, size_t ws_bytes, wc_stream_t stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (!res) return WC_ERR_ARG;
+    ConvArgs a;
+    const int rc = conv_prepare(a, xhi, xlo, xscale, wimage, wscale, bias, zero_line, g, 0, y, ws, ws_bytes);
+    if (rc != WC_OK) return rc;
+    if (!wc_conv_res_supported(g)) return WC_ERR_SHAPE;
+    const hipError_t e = (g->Cout % 256) == 0 ? launch_conv<2, 4, true>(a, st) : launch_conv<2, 2, true>(a, st);
+    if (e != hipSuccess) return (int)e;
+    const int64_t n4 = (int64_t)g->N * g->Hout * g->Wout * g->Cout / 4;
+    hipLaunchKernelGGL(conv_ksplit_reduce_res_kernel, dim3(grid_for(n4)), dim3(256), 0, st, (const float*)ws, a.ksplit, n4, g->Cout,
+                       xscale, wscale, bias, res, y);
+    return (int)hipGetLastError();
+}
+
+int wc_conv_block_dx_f32(const float* dx1, const float* x, const float* other, int64_t N, int64_t H, int64_t W, int C, int down,
+                         float* out, wc_stream_t stream)
+{
+    if (!dx1 || !x || !other || !out) return WC_ERR_NULL;
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || H > 0x7fffffff || W > 0x7fffffff) return WC_ERR_SHAPE;
+    if (down && ((H & 1) || (W & 1))) return WC_ERR_SHAPE;
+    const int64_t n4 = N * H * W * (C >> 2);
+    hipStream_t st = (hipStream_t)stream;
+    if (down) hipLaunchKernelGGL(conv_block_dx_kernel<true>, dim3(grid_for(n4)), dim3(256), 0, st, dx1, x, other, n4, C >> 2, (int)W, (int)H, out);
+    else      hipLaunchKernelGGL(conv_block_dx_kernel<false>, dim3(grid_for(n4)), dim3(256), 0, st, dx1, x, other, n4, C >> 2, (int)W, (int)H, out);
     return (int)hipGetLastError();
 }
 

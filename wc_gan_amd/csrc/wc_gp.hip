@@ -60,16 +60,42 @@ __device__ __forceinline__ float wave_max(float m)
     return m;
 }
 
+// colsum (nullable) / c4n = C / 4: the bias gradient's partial rows, of the MASKED values (the tensor the premultiplied route hands its
+// split), in conv_absmax_kernel's / conv_split_hist_kernel's grid, stride and LDS fold (wc_conv.hip): the rows have their bits
+__device__ __forceinline__ f32x4 colsum_add(f32x4 cs, f32x4 v)
+{
+    #pragma unroll
+    for (int j = 0; j < 4; ++j) cs[j] = __fadd_rn(cs[j], v[j]);      // (never contracted with the mask's multiply)
+    return cs;
+}
+
+__device__ __forceinline__ void colsum_fold(f32x4* red4, float* __restrict__ colsum, int c4n)
+{
+    if (colsum && (int)threadIdx.x < c4n) {
+        f32x4 s = red4[threadIdx.x];
+        for (int p = threadIdx.x + c4n; p < 256; p += c4n) s += red4[p];
+        *reinterpret_cast<f32x4*>(colsum + (int64_t)blockIdx.x * 4 * c4n + 4 * threadIdx.x) = s;
+    }
+}
+
 __global__ __launch_bounds__(256) void gp_absmax_kernel(const float* __restrict__ t, const float* __restrict__ a, int64_t n4, float slope,
-                                                        float* __restrict__ partial)
+                                                        float* __restrict__ partial, float* __restrict__ colsum = nullptr, int c4n = 0)
 {
     __shared__ float red[4];
+    __shared__ f32x4 red4[256];
     float m = 0.f;
-    for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) m = absmax4(m, masked_load(t, a, i, slope));
+    f32x4 cs = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const f32x4 v = masked_load(t, a, i, slope);
+        m = absmax4(m, v);
+        cs = colsum_add(cs, v);
+    }
     m = wave_max(m);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    if (colsum) red4[threadIdx.x] = cs;
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    colsum_fold(red4, colsum, c4n);
 }
 
 __global__ __launch_bounds__(256) void gp_split_kernel(const float* __restrict__ t, const float* __restrict__ a, int64_t n4, float slope,
@@ -108,9 +134,10 @@ __global__ __launch_bounds__(kAmaxBlocks) void gp_hist_seed_kernel(float* __rest
 // one launch, the scale from the record the call before left (conv_split_hist_kernel's protocol, word for word)
 __global__ __launch_bounds__(256) void gp_split_hist_kernel(const float* __restrict__ t, const float* __restrict__ a, int64_t n4, float slope,
                                                             _Float16* __restrict__ hi, _Float16* __restrict__ lo, float* __restrict__ scale_out,
-                                                            float* __restrict__ hist)
+                                                            float* __restrict__ hist, float* __restrict__ colsum, int c4n)
 {
     __shared__ float red[4];
+    __shared__ f32x4 red4[256];
     float mx[2] = {0.f, 0.f};
     int tlo[2] = {0x7fffffff, 0x7fffffff}, thi[2] = {0, 0};
     #pragma unroll
@@ -138,18 +165,22 @@ __global__ __launch_bounds__(256) void gp_split_hist_kernel(const float* __restr
     const float s = scale_for(assumed * kHistMargin);
     if (blockIdx.x == 0 && threadIdx.x == 0) { scale_out[0] = s; hist[2 * kHistArray + 2 + (1 - src)] = assumed; }
     float m = 0.f;
+    f32x4 cs = {0.f, 0.f, 0.f, 0.f};
     for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         const f32x4 v = masked_load(t, a, i, slope);
+        cs = colsum_add(cs, v);
         m = absmax4(m, v);
         store_split(v, s, hi, lo, i);
     }
     m = wave_max(m);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    if (colsum) red4[threadIdx.x] = cs;
     __syncthreads();
     if (threadIdx.x == 0) {
         const f32x2h p = {fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), __builtin_bit_cast(float, tag)};
         *reinterpret_cast<f32x2h*>(hist + (1 - src) * kHistArray + 2 * blockIdx.x) = p;
     }
+    colsum_fold(red4, colsum, c4n);
 }
 
 // the gated second pass (conv_split_redo_kernel's verdict and window)
@@ -236,32 +267,42 @@ __global__ __launch_bounds__(64) void gp_finish_kernel(const double* __restrict_
 
 extern "C" {
 
+static bool colsum_args_ok(const float* colsum_partials, int C, int64_t n)
+{
+    return !colsum_partials || (C > 0 && !(C & 3) && 256 % (C >> 2) == 0 && n % C == 0);      // wc_conv.hip's split_measured / split_hist
+}
+
 int wc_conv_split_masked_f32(const float* t, const float* a, int64_t n, float slope, void* hi, void* lo, float* scale, void* amax_scratch,
-                             wc_stream_t stream)
+                             float* colsum_partials, int C, wc_stream_t stream)
 {
     if (!t || !a || !hi || !lo || !scale || !amax_scratch || n <= 0 || (n & 3)) return WC_ERR_ARG;
     if (!(slope >= 0.f && slope <= 1.f)) return WC_ERR_ARG;
+    if (!colsum_args_ok(colsum_partials, C, n)) return WC_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(gp_absmax_kernel, dim3(kAmaxBlocks), dim3(256), 0, st, t, a, n / 4, slope, (float*)amax_scratch);
+    hipLaunchKernelGGL(gp_absmax_kernel, dim3(kAmaxBlocks), dim3(256), 0, st, t, a, n / 4, slope, (float*)amax_scratch,
+                       colsum_partials, colsum_partials ? C >> 2 : 0);
     hipLaunchKernelGGL(gp_split_kernel, dim3(grid_for(n / 4)), dim3(256), 0, st, t, a, n / 4, slope, (const float*)amax_scratch,
                        (_Float16*)hi, (_Float16*)lo, scale);
     return (int)hipGetLastError();
 }
 
-int wc_conv_split_hist_masked_f32(const float* t, const float* a, int64_t n, float slope, void* hi, void* lo, float* scale, float* hist,
-                                  int bootstrap, wc_stream_t stream)
+int wc_conv_split_hist_masked_f32(const float* t, const float* a, int64_t n, float slope, void* hi, void* lo, float* scale,
+                                  float* colsum_partials, int C, float* hist, int bootstrap, wc_stream_t stream)
 {
     if (!t || !a || !hi || !lo || !scale || !hist || n <= 0 || (n & 3)) return WC_ERR_ARG;
     if (!(slope >= 0.f && slope <= 1.f)) return WC_ERR_ARG;
+    if (!colsum_args_ok(colsum_partials, C, n)) return WC_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
+    const int c4n = colsum_partials ? C >> 2 : 0;
     if (bootstrap & 1) {
-        hipLaunchKernelGGL(gp_absmax_kernel, dim3(kAmaxBlocks), dim3(256), 0, st, t, a, n / 4, slope, hist);
+        hipLaunchKernelGGL(gp_absmax_kernel, dim3(kAmaxBlocks), dim3(256), 0, st, t, a, n / 4, slope, hist, colsum_partials, c4n);
         hipLaunchKernelGGL(gp_split_kernel, dim3(grid_for(n / 4)), dim3(256), 0, st, t, a, n / 4, slope, (const float*)hist, (_Float16*)hi,
                            (_Float16*)lo, scale);
         hipLaunchKernelGGL(gp_hist_seed_kernel, dim3(1), dim3(kAmaxBlocks), 0, st, hist);
         return (int)hipGetLastError();
     }
-    hipLaunchKernelGGL(gp_split_hist_kernel, dim3(kAmaxBlocks), dim3(256), 0, st, t, a, n / 4, slope, (_Float16*)hi, (_Float16*)lo, scale, hist);
+    hipLaunchKernelGGL(gp_split_hist_kernel, dim3(kAmaxBlocks), dim3(256), 0, st, t, a, n / 4, slope, (_Float16*)hi, (_Float16*)lo, scale, hist,
+                       colsum_partials, c4n);
     if (!(bootstrap & 2)) {
         const unsigned g2 = grid_for(n / 4) < 64 ? grid_for(n / 4) : 64u;
         hipLaunchKernelGGL(gp_split_redo_kernel, dim3(g2), dim3(256), 0, st, t, a, n / 4, slope, (_Float16*)hi, (_Float16*)lo, scale, hist);

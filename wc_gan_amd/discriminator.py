@@ -37,7 +37,40 @@ class ResBlockDown(nn.Module):
         if self.has_shortcut:
             self.shortcut = conv_layer(in_ch, nfilters, (1, 1), name=name + '.shortcut')
 
+    def _fusable(self):
+        """The part of _fused_plans that does not depend on the input: a block behind the first, no norm at either site (the identity
+        stack of norm 'n'), Conv2D layers of stride 1 with fp32 weights, the route switched on."""
+        from . import conv as fc, generator as _g
+        if self.is_first or not (fc.FUSED_BLOCK and _g.FAST_CONV):
+            return False
+        if not all(isinstance(bn, _g._UnfusedStack) and bn.norm_layer is None and len(bn.branches) == 0 for bn in (self.bn1, self.bn2)):
+            return False
+        convs = [self.conv1, self.conv2] + ([self.shortcut] if self.has_shortcut else [])
+        return all(isinstance(c, Conv2D) and c.kind == 'same' and c.conv.weight.dtype == torch.float32 for c in convs)
+
+    def _fused_plans(self, x):
+        """The three convolutions' plans when the block runs as one autograd node (conv.critic_block), else None: _fusable(), a dense fp32
+        NHWC input on the GPU, shapes the convolution kernel takes."""
+        from . import conv as fc, generator as _g
+        if not self._fusable():
+            return None
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
+                and getattr(x, '_wc_planes', None) is None and _g.split_of(x) is None):
+            return None
+        return fc.critic_block_plans(tuple(x.shape), tuple(self.conv1.conv.weight.shape), tuple(self.conv2.conv.weight.shape),
+                                     tuple(self.shortcut.conv.weight.shape) if self.has_shortcut else None, self.resample == 'DOWN')
+
     def forward(self, x, cls):
+        plans = self._fused_plans(x)
+        if plans is not None:
+            from . import conv as fc
+            w1, w2 = self.conv1._weight(), self.conv2._weight()
+            ws = self.shortcut._weight() if self.has_shortcut else None
+            x = self.bn1(x, cls)        # the identity (_fused_plans checked): called so that a forward hook on the site sees its tensor
+            y, h = fc.critic_block(x, w1, self.conv1.conv.bias, w2, self.conv2.conv.bias, ws, self.shortcut.conv.bias if self.has_shortcut else None,
+                                   (self.conv1, self.conv2, self.shortcut if self.has_shortcut else None), plans, self.resample == 'DOWN')
+            self.bn2(h, cls)            # likewise
+            return y
         # relu -> conv as one layer call: on the fast path the ReLU happens while the activation is split
         h = self.conv1(x) if self.is_first else self.conv1.forward_relu(self.bn1(x, cls))
         h = self.bn2(h, cls)
