@@ -876,6 +876,48 @@ size_t wc_gp_rows_workspace_bytes(int64_t N);
 int wc_gp_rows_f32(const float* g, int64_t N, int64_t L, double lambda, double inv_n, float* norms /*[N]*/, float* v /*[N,L]*/,
                    float* penalty /*[1]*/, void* ws, size_t ws_bytes, wc_stream_t stream);
 
+/* ==== Adam with the recipes' learning-rate schedules (run.py:99-144, --lr_decay_schedule), DESIGN.md section 4.18 ===========================
+ * Additive like the blocks above: WC_CORE_API keeps its list and WC_ABI_VERSION its value.  Stream-ordered and graph-capturable; nothing
+ * allocates or synchronises.  The update counter and the step's scalars are DEVICE values, so a replayed graph advances the schedule. */
+
+/* One launch per optimiser step.  counter[0] = it, the number of updates already applied (int64, 8-byte aligned).  Writes
+ *     record[0] = lr mult(it) / (1 - beta1^(it+1)),  record[1] = 1 / sqrt(1 - beta2^(it+1)),  record[2] = lr mult(it),  record[3] = mult(it)
+ * (float64 arithmetic, rounded once; record 16-byte aligned) and then counter[0] = it + 1.  kind / mult:
+ *     0 none         1
+ *     1 linear       max(0, 1 - it / total)
+ *     2 half-linear  the linear value while it < total / 2, then 0.5
+ *     3 linear-end   min(1, max(0, (total - it) / (total - 0.828 total)))
+ *     4 dropat       (it < drop_at ? 1 : 0.1) max(0, 1 - it / total)
+ * total > 0 unless kind == 0; drop_at is read by kind 4 alone. */
+int wc_adam_tick(int64_t* counter, float* record /*[4]*/, double lr, double beta1, double beta2, int kind, double total, double drop_at,
+                 wc_stream_t stream);
+
+/* The tensors of one update launch, passed to the kernel BY VALUE (3088 bytes of the 4 KiB kernel-argument segment): a network with
+ * more than WC_ADAM_CAPACITY tensors takes further launches.  Tensor i: numel[i] fp32 parameters at param[i], their gradients at grad[i]
+ * (the same element order), its moments at moment_off[i] elements into the flat buffers (a multiple of 4).  The launch has
+ * chunk_start[count] workgroups of `chunk` elements (a multiple of 1024); tensor i owns the workgroups
+ * chunk_start[i] .. chunk_start[i + 1] - 1 = ceil(numel[i] / chunk) of them, chunk_start[0] = 0. */
+#define WC_ADAM_CAPACITY 96
+typedef struct {
+    float*       param[WC_ADAM_CAPACITY];
+    const float* grad[WC_ADAM_CAPACITY];
+    int64_t      moment_off[WC_ADAM_CAPACITY];
+    int32_t      numel[WC_ADAM_CAPACITY];
+    int32_t      chunk_start[WC_ADAM_CAPACITY + 1];
+    int32_t      count, chunk;
+} wc_adam_table;
+int wc_adam_capacity(void);       /* WC_ADAM_CAPACITY, for a binding to check its struct against */
+
+/* For every element of every tensor of the table, with a = record[0], r = record[1] (torch.optim.Adam's formula, no weight decay):
+ *     exp_avg    <- exp_avg + (1 - beta1) (g - exp_avg)                (beta1 == 0: exp_avg is g; the buffer is not touched, may be NULL)
+ *     exp_avg_sq <- beta2 exp_avg_sq + (1 - beta2) g g                 (both moments formed in float64, rounded once)
+ *     p          <- p - a exp_avg / (sqrt(exp_avg_sq) r + eps)
+ * 16-byte accesses for a tensor whose param and grad pointers are both 16-byte aligned, 4-byte accesses otherwise (a gradient that is a
+ * view into a flat bucket); the flat moment buffers are 16-byte aligned and hold `moment_elems` floats.  Every table entry is checked
+ * against its chunk count and `moment_elems` before the launch (WC_ERR_SHAPE / WC_ERR_ARG). */
+int wc_adam_update_f32(const wc_adam_table* table, float* exp_avg /*nullable when beta1 == 0*/, float* exp_avg_sq, int64_t moment_elems,
+                       const float* record, double beta1, double beta2, float eps, wc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

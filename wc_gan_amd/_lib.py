@@ -202,7 +202,18 @@ SIGNATURES = {
     "wc_gp_interp_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "wc_gp_rows_workspace_bytes": (c_size_t, [c_int64]),
     "wc_gp_rows_f32": (c_int, [c_void_p, c_int64, c_int64, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wc_adam_capacity": (c_int, []),
+    "wc_adam_tick": (c_int, [c_void_p, c_void_p, c_double, c_double, c_double, c_int, c_double, c_double, c_void_p]),
+    "wc_adam_update_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_double, c_double, c_float, c_void_p]),
 }
+
+ADAM_CAPACITY = 96       # WC_ADAM_CAPACITY
+
+
+class AdamTable(ctypes.Structure):       # wc_adam_table
+    _fields_ = [("param", c_void_p * ADAM_CAPACITY), ("grad", c_void_p * ADAM_CAPACITY), ("moment_off", c_int64 * ADAM_CAPACITY),
+                ("numel", ctypes.c_int32 * ADAM_CAPACITY), ("chunk_start", ctypes.c_int32 * (ADAM_CAPACITY + 1)),
+                ("count", ctypes.c_int32), ("chunk", ctypes.c_int32)]
 
 
 class SnItem(ctypes.Structure):          # wc_sn_item

@@ -121,7 +121,9 @@ def _bump_versions(params):
 class GanTrainer:
     def __init__(self, generator, discriminator, batch_size=64, generator_batch_multiple=2, training_ratio=5,
                  lr=2e-4, beta1=0.0, beta2=0.9, noise_dim=128, number_of_classes=10, conditional=False,
-                 process_group=None, seed=1234, flat_buckets=None, objective='hinge', gradient_penalty_weight=0.0):
+                 process_group=None, seed=1234, flat_buckets=None, objective='hinge', gradient_penalty_weight=0.0,
+                 lr_decay_schedule=None, number_of_epochs=None, schedule_iters=None, generator_lr=None, discriminator_lr=None,
+                 optimizer=None):
         if objective not in ('hinge', 'wgan'):
             raise ValueError(f"objective {objective!r}: 'hinge' or 'wgan' (run.py --*_adversarial_objective)")
         # 'wgan' (scripts/cifar10_resnet_wgan_*.sh): the critic loss E D(fake) - E D(real), plus gradient_penalty_weight x the gradient
@@ -141,8 +143,24 @@ class GanTrainer:
         # fused: one multi-tensor kernel per update instead of ~10 small launches per parameter (step counters on the
         # device either way)
         kw = dict(fused=True) if cap else dict()
-        self.opt_g = torch.optim.Adam(self.g_bucket.params, lr=lr, betas=(beta1, beta2), capturable=cap, **kw)
-        self.opt_d = torch.optim.Adam(self.d_bucket.params, lr=lr, betas=(beta1, beta2), capturable=cap, **kw)
+        if optimizer not in (None, 'hip'):
+            raise ValueError(f"optimizer {optimizer!r}: None (torch.optim.Adam) or 'hip' (optim.ScheduledAdam)")
+        g_lr = lr if generator_lr is None else generator_lr                # run.py:252-253 --generator_lr / --discriminator_lr
+        d_lr = lr if discriminator_lr is None else discriminator_lr
+        if optimizer == 'hip' or lr_decay_schedule is not None:
+            # run.py:100-101: the generator's schedule runs over 1000 x number_of_epochs of ITS updates, the critic's over training_ratio
+            # times as many of its own (optim.py; each optimiser counts its updates on the device, so graph replays advance the rate)
+            from .optim import ScheduledAdam
+            total = schedule_iters if schedule_iters is not None else (None if number_of_epochs is None else 1000 * number_of_epochs)
+            if lr_decay_schedule is not None and total is None:
+                raise ValueError("lr_decay_schedule needs number_of_epochs (or schedule_iters, the generator's total directly)")
+            d_total = None if total is None else total * training_ratio
+            self.opt_g = ScheduledAdam(self.g_bucket.params, g_lr, (beta1, beta2), schedule=lr_decay_schedule, total_iters=total, ratio=1)
+            self.opt_d = ScheduledAdam(self.d_bucket.params, d_lr, (beta1, beta2), schedule=lr_decay_schedule, total_iters=d_total,
+                                       ratio=training_ratio)
+        else:
+            self.opt_g = torch.optim.Adam(self.g_bucket.params, lr=g_lr, betas=(beta1, beta2), capturable=cap, **kw)
+            self.opt_d = torch.optim.Adam(self.d_bucket.params, lr=d_lr, betas=(beta1, beta2), capturable=cap, **kw)
         if cap:
             # the default device generator (its Philox offset is graph-safe); every replica draws its own noise
             rank = dist.get_rank(process_group) if (dist.is_available() and dist.is_initialized()) else 0
@@ -469,6 +487,19 @@ WGAN_CONFIGS = {'cifar10_wgan_uncond': dict(
     discriminator=dict(input_image_shape=(32, 32, 3), block_sizes=(128, 128, 128, 128), resamples=('DOWN', 'DOWN', 'SAME', 'SAME'),
                        number_of_classes=10, type=None, spectral=False, sum_pool=True),
     image_shape=(32, 32, 3), conditional=False, objective='wgan', gradient_penalty_weight=10)}
+
+
+# --lr_decay_schedule / --number_of_epochs of each recipe's script: GanTrainer's arguments of the same names (the config tables above carry
+# the networks alone and are left as they are).  build_trainer(CONFIGS[name], **RECIPE_SCHEDULES[name]) trains the recipe at its script's rates.
+RECIPE_SCHEDULES = {
+    'cifar10_uncond': dict(lr_decay_schedule='linear', number_of_epochs=50),            # scripts/cifar10_resnet_sn_uncond.sh:7
+    'cifar10_cond': dict(lr_decay_schedule='dropat30', number_of_epochs=50),            # scripts/cifar10_resnet_sn_cond.sh:8
+    'stl10_uncond': dict(lr_decay_schedule='linear', number_of_epochs=100),             # scripts/stl10_resnet_sn_uncond.sh:7
+    'tinyimagenet_cond_sa': dict(lr_decay_schedule='linear', number_of_epochs=100),     # scripts/tinyimagenet_resnet_sn_cond_sa.sh:7
+    'cifar10_dcgan_uncond': dict(lr_decay_schedule='linear', number_of_epochs=100),     # scripts/cifar10_dcgan_sn_uncond.sh:7
+    'stl10_dcgan_uncond': dict(lr_decay_schedule='linear', number_of_epochs=200),       # scripts/stl10_dcgan_sn_uncond.sh:7
+    'cifar10_wgan_uncond': dict(lr_decay_schedule='linear', number_of_epochs=100),      # scripts/cifar10_resnet_wgan_uncond.sh:7
+}
 
 
 def dcgan_sites(config, batch):
