@@ -630,6 +630,32 @@ int wc_conv_weights_pair_f32(const float* w, int64_t stride_r, int64_t stride_s,
                              float* scale, void* amax_scratch, const float* known_amax, int known_count,
                              wc_stream_t stream);
 
+/* The images of MANY weights in one launch: a pass's images depend on its weights only, so a network builds them all at the top of
+ * the pass instead of one launch per layer between the layer's split and its convolution.  `jobs` is a HOST array (its contents travel
+ * in the kernel arguments: no copy to the device, no allocation; capturable like the per-layer entries).  Every field as in
+ * wc_conv_weights_f32, and the image and the scale have its bits; `scale` is ONE float per job.  `amax`: `amax_count` (1..4096) device
+ * floats whose maximum is max|w| -- the spectral-norm op's, or the WC_CONV_ABSMAX_FLOATS partials wc_conv_absmax_batch_f32 left --; NULL:
+ * the maximum is taken inside the job (n_elems <= 32768, n_elems % 4 == 0, w 16-byte aligned: wc_conv_weights_f32's rule; WC_ERR_ARG
+ * otherwise).  `pair_of`: -1, or the index (smaller than the job's own) of the other image of the SAME weight -- a layer's forward and
+ * data-gradient image stay two jobs; the entry checks that both read the same source and maximum and come to the same scale
+ * (WC_ERR_ARG otherwise, as wc_conv_weights_pair_f32).  Any count > 0: a list that does not fit one launch's arguments (16 jobs, 6
+ * distinct tap-source tables) takes several, filled greedily; wc_conv_weights_batch_launches says how many (or a negative error).
+ * Errors (nothing is launched): WC_ERR_NULL a null list or field, WC_ERR_SHAPE count <= 0, WC_ERR_ARG a job the per-layer entry refuses. */
+typedef struct {
+    const float* w; int64_t stride_k, stride_n, stride_r, stride_s, n_elems;
+    const wc_conv_geom* g; void* image; float* scale;
+    const float* amax; int amax_count; int pair_of;
+} wc_conv_weights_job;
+int wc_conv_weights_batch_f32(const wc_conv_weights_job* jobs, int count, wc_stream_t stream);
+int wc_conv_weights_batch_launches(const wc_conv_weights_job* jobs, int count);
+
+/* max|x| of many tensors in one launch (the weights no spectral norm has measured): per job WC_CONV_ABSMAX_FLOATS per-workgroup maxima
+ * of the n floats at x (16-byte aligned) in `partial`, the ones wc_conv_weights_f32's own sweep leaves in its scratch, bit for bit.
+ * Same error rules. */
+#define WC_CONV_ABSMAX_FLOATS 512
+typedef struct { const float* x; int64_t n; float* partial; } wc_conv_absmax_job;
+int wc_conv_absmax_batch_f32(const wc_conv_absmax_job* jobs, int count, wc_stream_t stream);
+
 /* y = conv(x, w) (+ bias[Cout]) (then max(., 0) when relu != 0) for the geometry; x as split planes, `zero_line` = 64
  * device bytes of zeros (the padding). */
 size_t wc_conv_workspace_bytes(const wc_conv_geom* g);     /* 0 unless the grid is small (the tap loop is then shared) */

@@ -154,6 +154,9 @@ SIGNATURES = {
                                        c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "wc_conv_weights_pair_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                          c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "wc_conv_weights_batch_f32": (c_int, [c_void_p, c_int, c_void_p]),
+    "wc_conv_weights_batch_launches": (c_int, [c_void_p, c_int]),
+    "wc_conv_absmax_batch_f32": (c_int, [c_void_p, c_int, c_void_p]),
     "wc_conv_wrw_workspace_bytes": (c_size_t, [c_void_p]),
     "wc_conv_wrw_f16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_int64, c_int64, c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
@@ -236,6 +239,18 @@ class ConvGeom(ctypes.Structure):        # wc_conv_geom
                 ("wr", ((ctypes.c_byte * 4) * 16) * 4), ("ws", ((ctypes.c_byte * 4) * 16) * 4),
                 ("wcoef", c_float)]
 
+
+class ConvWeightsJob(ctypes.Structure):  # wc_conv_weights_job
+    _fields_ = [("w", c_void_p), ("stride_k", c_int64), ("stride_n", c_int64), ("stride_r", c_int64), ("stride_s", c_int64),
+                ("n_elems", c_int64), ("g", c_void_p), ("image", c_void_p), ("scale", c_void_p), ("amax", c_void_p),
+                ("amax_count", c_int), ("pair_of", c_int)]
+
+
+class ConvAbsmaxJob(ctypes.Structure):   # wc_conv_absmax_job
+    _fields_ = [("x", c_void_p), ("n", c_int64), ("partial", c_void_p)]
+
+
+ABSMAX_FLOATS = 512      # WC_CONV_ABSMAX_FLOATS
 
 _lib = None
 

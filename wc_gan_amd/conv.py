@@ -298,8 +298,13 @@ def _storage_extent(w):
     return 1 + sum((n - 1) * s for n, s in zip(w.shape, w.stride()))
 
 
-def weight_image(w, geom, k_axis, n_axis):
-    """Fragment image of a (dense) 4-d weight for a geometry; k_axis / n_axis = which axis is reduced / produced."""
+def weight_image(w, geom, k_axis, n_axis, site=None):
+    """Fragment image of a (dense) 4-d weight for a geometry; k_axis / n_axis = which axis is reduced / produced.
+    site: the layer object whose own weight w is -- the image prepare_images() built for it in this pass is picked up (see there)."""
+    if site is not None:
+        got = _pick_up(site, w, ((geom, k_axis, n_axis),))
+        if got is not None:
+            return got
     lib = _lib.load()
     nbytes = lib.wc_conv_weights_bytes(ctypes.addressof(geom))
     img = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
@@ -315,8 +320,12 @@ def weight_image(w, geom, k_axis, n_axis):
     return img, scale
 
 
-def weight_image_pair(w, fwd, bwd):
-    """The forward and the data-gradient image of one weight in one launch; fwd / bwd = (geometry, k_axis, n_axis)."""
+def weight_image_pair(w, fwd, bwd, site=None):
+    """The forward and the data-gradient image of one weight in one launch; fwd / bwd = (geometry, k_axis, n_axis).  site: as in weight_image."""
+    if site is not None:
+        got = _pick_up(site, w, (fwd, bwd))
+        if got is not None:
+            return got
     lib = _lib.load()
     (ga, ka, na), (gb, kb, nb) = fwd, bwd
     img_a = torch.empty(lib.wc_conv_weights_bytes(ctypes.addressof(ga)), dtype=torch.uint8, device=w.device)
@@ -340,6 +349,161 @@ def _cached_image(w, key, geom, k_axis, n_axis):
     counter, and a stale image is a silently wrong convolution; the reuse it bought (the generator's 7 weights, twice per
     step) was ~0.1 ms."""
     return weight_image(w, geom, k_axis, n_axis)
+
+
+# ---- a pass's weight images in one launch -------------------------------------------------------------------------------------------------
+# The images depend on the weights only, yet each was a launch of its own between its layer's split and its convolution, on a chain of
+# dependent dispatches (8 per critic pass).  As spectral.prepare_spectral does for the normalised weights, a network builds them at
+# the top of its pass: the first pass under a key (pass_key: what fixes which images a pass asks for) LOGS the requests that name their
+# layer; later passes under that key build every logged image from the weights as they are THEN (build_images: one launch, plus one for
+# the maxima of weights no spectral norm has measured) and leave them on the layers, which pick them up once.  Nothing outlives its pass:
+# no per-version cache (see _cached_image), so fused Adam and replayed hipGraphs, which move weights without moving `_version`, cannot meet
+# a stale image -- a replayed graph replays the build, in front of its layers, on the updated weights.  A layer takes a prepared image only
+# if it was built from the very tensor object the layer holds, for the very geometry object it asks with; otherwise it builds its own as
+# before, so a wrong or stale log costs launches and nothing else (and is dropped, to be logged again).  BATCH_IMAGES = False: every layer
+# builds its own (tests and tools compare the two in one process).
+# The critic prepares (discriminator.Discriminator.forward).  The generator does not: with its forward prepared the same way the step was
+# 0.04-0.1 ms SLOWER than without (profiles/image_batch_step_ab.txt; the cause was not looked for -- its passes run beside the critic on
+# a second stream, or put their shortcuts on one, so its per-layer launches are not on one chain as the critic's are).
+BATCH_IMAGES = True
+_recording = None           # (root, key, entries) while a pass without a log runs
+_prepared = None            # [root, key, missed] while a pass with prepared images runs
+
+
+def pass_key(root, x):
+    return (tuple(x.shape), torch.is_grad_enabled(), bool(x.requires_grad), root.training,
+            tuple(p.requires_grad for p in root.parameters()))
+
+
+def _own_weight(site):
+    """The weight tensor a layer will hand to its convolution in this pass, without taking it: the parameter itself, or what
+    prepare_spectral left for the layer to pick up (None when nothing valid is waiting: the layer then normalises, and builds, on its own)."""
+    conv = getattr(site, 'conv', None)
+    if conv is None:
+        return None
+    if hasattr(conv, 'normalized_weight'):
+        ready = getattr(conv, '_w_ready', None)
+        if ready is None or ready[1] != conv.weight._version or ready[2] != conv.training:
+            return None
+        return ready[0]
+    return conv.weight
+
+
+def _same_geoms(a, b):
+    return len(a) == len(b) and all(p[0] is q[0] and p[1] == q[1] and p[2] == q[2] for p, q in zip(a, b))
+
+
+def build_images(requests):
+    """requests: [(weight, ((geometry, k_axis, n_axis), ...one or two...))] -> per request a tuple of (image, scale) per geometry, with the
+    bits of weight_image / weight_image_pair: wc_conv_weights_batch_f32 behind, where a weight's maximum is neither known nor taken inside
+    its job, one wc_conv_absmax_batch_f32.  All images of the call share one allocation."""
+    lib = _lib.load()
+    dev = requests[0][0].device
+    sizes = [[lib.wc_conv_weights_bytes(ctypes.addressof(g[0])) for g in geoms] for _, geoms in requests]
+    njobs = sum(len(s) for s in sizes)
+    images = torch.empty(sum(sum(s) for s in sizes), dtype=torch.uint8, device=dev)
+    scales = torch.empty(njobs, dtype=torch.float32, device=dev)
+    jobs = (_lib.ConvWeightsJob * njobs)()
+    measure = []
+    for w, _ in requests:
+        ext = _storage_extent(w)
+        if ext != w.numel():
+            raise ValueError("weight must be dense")
+        if getattr(w, '_wc_amax', None) is None and not (ext <= 32768 and ext % 4 == 0 and w.data_ptr() % 16 == 0):
+            measure.append(w)
+    partials = None
+    if measure:
+        partials = torch.empty(len(measure) * _lib.ABSMAX_FLOATS, dtype=torch.float32, device=dev)
+        sweeps = (_lib.ConvAbsmaxJob * len(measure))()
+        for i, w in enumerate(measure):
+            sweeps[i].x, sweeps[i].n, sweeps[i].partial = w.data_ptr(), w.numel(), partials.data_ptr() + 4 * _lib.ABSMAX_FLOATS * i
+        _lib.check(lib.wc_conv_absmax_batch_f32(ctypes.addressof(sweeps), len(measure), _stream()), "wc_conv_absmax_batch_f32")
+    out, j, off, m = [], 0, 0, 0
+    for (w, geoms), nbytes in zip(requests, sizes):
+        known = getattr(w, '_wc_amax', None)
+        if known is not None:
+            amax, count = known.data_ptr(), known.numel()
+        elif m < len(measure) and measure[m] is w:
+            amax, count = partials.data_ptr() + 4 * _lib.ABSMAX_FLOATS * m, _lib.ABSMAX_FLOATS
+            m += 1
+        else:
+            amax, count = None, 0
+        res = []
+        for i, ((g, k_axis, n_axis), nb) in enumerate(zip(geoms, nbytes)):
+            job = jobs[j]
+            job.w, job.n_elems, job.g = w.data_ptr(), w.numel(), ctypes.addressof(g)
+            job.stride_k, job.stride_n, job.stride_r, job.stride_s = w.stride(k_axis), w.stride(n_axis), w.stride(2), w.stride(3)
+            job.image, job.scale = images.data_ptr() + off, scales.data_ptr() + 4 * j
+            job.amax, job.amax_count, job.pair_of = amax, count, (j - 1 if i else -1)
+            res.append((images[off:off + nb], scales[j:j + 1]))
+            j += 1
+            off += nb
+        out.append(tuple(res))
+    _lib.check(lib.wc_conv_weights_batch_f32(ctypes.addressof(jobs), njobs, _stream()), "wc_conv_weights_batch_f32")
+    return out
+
+
+def _clear_images(root):
+    for site in root.__dict__.get('_wc_image_sites', ()):
+        site._wc_images = None
+    root._wc_image_sites = ()
+
+
+def prepare_images(root, key):
+    """Call at the top of a network's forward (behind prepare_spectral), finish_images(root) when the pass ends.  See above."""
+    global _recording, _prepared
+    _clear_images(root)                         # (a pass that did not end)
+    _recording = _prepared = None
+    if not BATCH_IMAGES:
+        return
+    logs = root.__dict__.get('_wc_image_logs')
+    if logs is None:
+        logs = root._wc_image_logs = {}
+    log = logs.get(key)
+    if log is None:
+        _recording = (root, key, [])
+        return
+    _prepared = [root, key, False]
+    requests, sites = [], []
+    for site, geoms in log:
+        w = _own_weight(site)
+        if w is not None and w.dtype == torch.float32 and w.dim() == 4:
+            requests.append((w, geoms))
+            sites.append(site)
+    if not requests:
+        return
+    for site, (w, geoms), images in zip(sites, requests, build_images(requests)):
+        if site.__dict__.get('_wc_images') is None:
+            site._wc_images = []
+        site._wc_images.append((w, geoms, images if len(geoms) > 1 else images[0]))
+    root._wc_image_sites = tuple(sites)
+
+
+def _pick_up(site, w, geoms):
+    """The images prepared for this request, once; None: the layer builds its own (and the request is logged, or the log marked stale)."""
+    recs = site.__dict__.get('_wc_images')
+    if recs:
+        for i, (rw, rgeoms, images) in enumerate(recs):
+            if rw is w and _same_geoms(rgeoms, geoms):
+                del recs[i]
+                return images
+    if _recording is not None:
+        _recording[2].append((site, tuple(geoms)))
+    elif _prepared is not None:
+        _prepared[2] = True
+    return None
+
+
+def finish_images(root):
+    global _recording, _prepared
+    if _recording is not None and _recording[0] is root:
+        root._wc_image_logs[_recording[1]] = _recording[2]
+    elif _prepared is not None and _prepared[0] is root:
+        # a request the log did not foresee, or a prepared image nobody took: log this key again on its next pass
+        if _prepared[2] or any(site.__dict__.get('_wc_images') for site in root.__dict__.get('_wc_image_sites', ())):
+            root._wc_image_logs.pop(_prepared[1], None)
+    _recording = _prepared = None
+    _clear_images(root)
 
 
 def run(planes, image, geom, bias=None, relu=False, nbytes=None, res=None):
@@ -457,9 +621,9 @@ class _FastConv(torch.autograd.Function):
         planes = handed if handed is not None else split_planes(x, relu=relu_input, site=site, role='x', leaky=leaky)
         ctx.site, ctx.leaky = site, leaky
         if ctx.needs_input_grad[0]:                 # the data gradient will want its image too: both in one launch
-            img, ctx.bwd_image = weight_image_pair(w, plan.fwd, plan.bwd)
+            img, ctx.bwd_image = weight_image_pair(w, plan.fwd, plan.bwd, site=site)
         else:
-            img, ctx.bwd_image = weight_image(w, gf, kf, nf), None
+            img, ctx.bwd_image = weight_image(w, gf, kf, nf, site=site), None
         # residual: y = conv(x) + residual, in the convolution's finish where it has one that takes it (plan.res), else added here
         if residual is not None and plan.res and FUSED_RESIDUAL:
             y = run(planes, img, gf, bias, nbytes=plan.fwd_ws, res=residual.contiguous())
@@ -534,11 +698,11 @@ class _SplitConv(torch.autograd.Function):
         ctx.site = site
         gf, kf, nf = plan.fwd
         wf, bf = ops.fold_channel_scale(w, bias, st.scale, st.center)
-        img = weight_image(wf, gf, kf, nf)
+        img = weight_image(wf, gf, kf, nf)          # (the folded weight is made inside the pass: nothing to prepare)
         ctx.bwd_image = None
         if ctx.needs_input_grad[0]:
             gb, kb, nb = plan.bwd
-            ctx.bwd_image = weight_image(w, gb, kb, nb)
+            ctx.bwd_image = weight_image(w, gb, kb, nb, site=site)
         hi, lo = st.planes[0].view(st.shape), st.planes[1].view(st.shape)
         one = _one(hi.device)
         y = run((hi, lo, one), img, gf, bf, nbytes=plan.fwd_ws)
@@ -791,12 +955,12 @@ def critic_block_plans(xshape, w1shape, w2shape, wsshape, down):
     return p1, p2, ps
 
 
-def _images(w, plan, both):
+def _images(w, plan, both, site=None):
     """(forward image, data-gradient image | None): _FastConv.forward's choice"""
     if both:
-        return weight_image_pair(w, plan.fwd, plan.bwd)
+        return weight_image_pair(w, plan.fwd, plan.bwd, site=site)
     gf, kf, nf = plan.fwd
-    return weight_image(w, gf, kf, nf), None
+    return weight_image(w, gf, kf, nf, site=site), None
 
 
 def _layer_gradients(g_planes, fused_db, x_planes, w, plan, bwd_image, need_dx, need_dw):
@@ -831,14 +995,14 @@ class _CriticBlock(torch.autograd.Function):
         need = ctx.needs_input_grad
         need_h = need[0] or need[1] or need[2]
         x_pl = split_planes(x, relu=True, site=conv1, role='x')
-        img1, bimg1 = _images(w1, p1, need[0])
+        img1, bimg1 = _images(w1, p1, need[0], conv1)
         h = run(x_pl, img1, p1.fwd[0], b1, nbytes=p1.fwd_ws)
         h_pl = split_planes(h, relu=True, site=conv2, role='x')
-        img2, bimg2 = _images(w2, p2, need_h)
+        img2, bimg2 = _images(w2, p2, need_h, conv2)
         s, s_pl, bimgs = x, (), None
         if ws is not None:
             s_pl = split_planes(_pool2(x) if down else x, site=shortcut, role='x')
-            imgs, bimgs = _images(ws, ps, need[0])
+            imgs, bimgs = _images(ws, ps, need[0], shortcut)
             s = run(s_pl, imgs, ps.fwd[0], bs, nbytes=ps.fwd_ws)
         if p2.res and FUSED_RESIDUAL:
             y = run(h_pl, img2, p2.fwd[0], b2, nbytes=p2.fwd_ws, res=s)

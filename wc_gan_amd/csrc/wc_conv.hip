@@ -32,6 +32,7 @@
 #include "wc_common.h"
 #include "../../include/wc_hip.h"
 #include <stdlib.h>
+#include <string.h>
 
 
 namespace {
@@ -679,6 +680,85 @@ __global__ __launch_bounds__(256) void conv_weights_pair_kernel(WeightArgs a, We
 {
     if ((int)blockIdx.x < blocks_a) conv_weights_body(a, blockIdx.x, blocks_a);
     else conv_weights_body(b, blockIdx.x - blocks_a, gridDim.x - blocks_a);
+}
+
+// ---- the images of MANY weights in one grid (wc_conv_weights_batch_f32) -----------------------------------------------------------------
+// A pass's images depend on its weights only, so they need not sit one launch each between a layer's split and its convolution.  The
+// role of a workgroup is a range of the linear block index (the idiom above); each job's workgroups run conv_weights_body on a
+// WeightArgs of their own.  680 bytes of WeightArgs per job would not fit the kernel arguments, and most of it is the tap-source tables,
+// which depend on the KIND of geometry only: the arguments carry a small record per job and the few distinct tables (r and s, both
+// 0..3, in one byte), and a workgroup puts its job's WeightArgs together in LDS.
+constexpr int kBatchJobs = 16, kBatchTables = 6;
+constexpr int kBatchBlocks = 16384;                 // workgroups of one launch (one job: at most grid_for's 2048)
+
+struct BatchJob {
+    const float* w; const float* amax; float* scale_out; char* img;
+    int64_t sk, sn, sr, ss, n4;
+    int K, Nn;
+    float coef, bound_mul;
+    int amax_count, table;
+};
+struct BatchTable {
+    int ntaps, nphase;
+    signed char nsrc[kMaxPhase][kMaxTaps];
+    unsigned char rs[kMaxPhase][kMaxTaps][4];       // r | s << 2
+};
+struct WeightBatch {
+    BatchJob job[kBatchJobs];
+    BatchTable table[kBatchTables];
+    int first[kBatchJobs + 1];
+    int count;
+};
+static_assert(sizeof(WeightBatch) <= 4096, "the batch travels in the kernel arguments");
+
+__global__ __launch_bounds__(256) void conv_weights_batch_kernel(WeightBatch q)
+{
+    __shared__ WeightArgs a;
+    int i = 0;
+    while (i + 1 < q.count && (int)blockIdx.x >= q.first[i + 1]) ++i;
+    const BatchJob& j = q.job[i];
+    const BatchTable& t = q.table[j.table];
+    if (threadIdx.x == 0) {
+        a.w = j.w; a.sk = j.sk; a.sn = j.sn; a.sr = j.sr; a.ss = j.ss;
+        a.amax = j.amax; a.scale_out = j.scale_out; a.img = j.img;
+        a.K = j.K; a.Nn = j.Nn; a.ntaps = t.ntaps; a.nphase = t.nphase;
+        a.n4 = j.n4; a.coef = j.coef; a.bound_mul = j.bound_mul; a.amax_count = j.amax_count;
+    }
+    for (int e = threadIdx.x; e < kMaxPhase * kMaxTaps * 4; e += 256) {
+        const int p = e / (kMaxTaps * 4), tp = (e >> 2) % kMaxTaps, m = e & 3;
+        const unsigned char v = t.rs[p][tp][m];
+        a.r[p][tp][m] = (signed char)(v & 3);
+        a.s[p][tp][m] = (signed char)(v >> 2);
+        if (m == 0) a.nsrc[p][tp] = t.nsrc[p][tp];
+    }
+    __syncthreads();
+    conv_weights_body(a, (int)blockIdx.x - q.first[i], q.first[i + 1] - q.first[i]);
+}
+
+// max|x| of many tensors in one grid: kAmaxBlocks workgroups per tensor, conv_absmax_kernel's mapping of elements to workgroups (the
+// same partials, so the same scale_of)
+constexpr int kAbsmaxJobs = 32;
+struct AbsmaxJob { const float* x; int64_t n; float* partial; };
+struct AbsmaxBatch { AbsmaxJob job[kAbsmaxJobs]; };
+
+__global__ __launch_bounds__(256) void conv_absmax_batch_kernel(AbsmaxBatch q)
+{
+    __shared__ float red[4];
+    const AbsmaxJob& j = q.job[blockIdx.x / kAmaxBlocks];
+    const int bid = blockIdx.x % kAmaxBlocks;
+    const float* __restrict__ x = j.x;
+    const int64_t n4 = j.n >> 2;
+    float m = 0.f;
+    for (int64_t i = bid * 256 + threadIdx.x; i < n4; i += (int64_t)kAmaxBlocks * 256) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * i);
+        m = fmaxf(fmaxf(m, fabsf(v[0])), fmaxf(fabsf(v[1]), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+    }
+    if (bid == 0 && threadIdx.x == 0) for (int64_t i = 4 * n4; i < j.n; ++i) m = fmaxf(m, fabsf(x[i]));
+    #pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) j.partial[bid] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
 // ---- weight gradient: dW[slice][ci][co] = sum over grid points of x[in pixel][ci] * gy[out pixel][co] -------------------
@@ -1396,6 +1476,115 @@ int wc_conv_weights_pair_f32(const float* w, int64_t stride_r, int64_t stride_s,
     const int blocks_a = grid_for((int64_t)ga->nphase * ga->ntaps * (ga->Cin >> 5) * (ga->Cout >> 5) * 128);
     const int blocks_b = grid_for((int64_t)gb->nphase * gb->ntaps * (gb->Cin >> 5) * (gb->Cout >> 5) * 128);
     hipLaunchKernelGGL(conv_weights_pair_kernel, dim3(blocks_a + blocks_b), dim3(256), 0, st, a, b, blocks_a);
+    return (int)hipGetLastError();
+}
+
+// the table of a geometry kind: the entries conv_weights_body reads (phase < nphase, tap < ntaps, source < nsrc), zero elsewhere
+static void fill_batch_table(BatchTable& t, const WeightArgs& a)
+{
+    memset(&t, 0, sizeof(t));
+    t.ntaps = a.ntaps; t.nphase = a.nphase;
+    for (int p = 0; p < a.nphase; ++p)
+        for (int k = 0; k < a.ntaps; ++k) {
+            t.nsrc[p][k] = a.nsrc[p][k];
+            for (int m = 0; m < a.nsrc[p][k]; ++m) t.rs[p][k][m] = (unsigned char)(a.r[p][k][m] | (a.s[p][k][m] << 2));
+        }
+}
+
+static int check_weights_job(const wc_conv_weights_job& j, WeightArgs& a)
+{
+    if (!j.w || !j.g || !j.image || !j.scale) return WC_ERR_NULL;
+    if (j.n_elems <= 0) return WC_ERR_ARG;
+    if (j.amax) { if (j.amax_count < 1 || j.amax_count > 4096) return WC_ERR_ARG; }
+    else if (j.n_elems > 32768 || (j.n_elems & 3) || ((uintptr_t)j.w & 15)) return WC_ERR_ARG;   // (wc_conv_weights_f32's rule for the maximum taken inside)
+    const int rc = fill_weight_args(a, j.w, j.stride_k, j.stride_n, j.stride_r, j.stride_s, j.n_elems, j.g, j.image, j.scale, j.amax,
+                                    j.amax ? j.amax_count : 0);
+    if (rc != WC_OK) return rc;
+    for (int p = 0; p < a.nphase; ++p)
+        for (int k = 0; k < a.ntaps; ++k)
+            for (int m = 0; m < a.nsrc[p][k]; ++m)
+                if (a.r[p][k][m] < 0 || a.r[p][k][m] > 3 || a.s[p][k][m] < 0 || a.s[p][k][m] > 3) return WC_ERR_ARG;
+    return WC_OK;
+}
+
+// checks every job, then fills launches greedily (a launch ends at kBatchJobs jobs, kBatchTables distinct tables or kBatchBlocks
+// workgroups); st == nullptr with launch == false: only counts them
+static int weights_batch(const wc_conv_weights_job* jobs, int count, bool launch, hipStream_t st, int* launches)
+{
+    if (!jobs) return WC_ERR_NULL;
+    if (count <= 0) return WC_ERR_SHAPE;
+    *launches = 0;
+    WeightArgs a, b;
+    for (int i = 0; i < count; ++i) {
+        int rc = check_weights_job(jobs[i], a);
+        if (rc != WC_OK) return rc;
+        const int p = jobs[i].pair_of;
+        if (p < 0) continue;
+        // the second image of a weight whose first is job p: one weight, one kind, the same scale both ways
+        if (p >= i) return WC_ERR_ARG;
+        rc = check_weights_job(jobs[p], b);
+        if (rc != WC_OK) return rc;
+        if (jobs[p].w != jobs[i].w || jobs[p].amax != jobs[i].amax || jobs[p].amax_count != jobs[i].amax_count
+            || jobs[p].n_elems != jobs[i].n_elems || a.bound_mul != b.bound_mul) return WC_ERR_ARG;
+    }
+    for (int c0 = 0; c0 < count;) {
+        WeightBatch q;
+        memset(&q, 0, sizeof(q));
+        int take = 0, blocks = 0, ntab = 0;
+        while (c0 + take < count && take < kBatchJobs) {
+            const wc_conv_weights_job& j = jobs[c0 + take];
+            (void)check_weights_job(j, a);
+            BatchTable t;
+            fill_batch_table(t, a);
+            int ti = 0;
+            while (ti < ntab && memcmp(&q.table[ti], &t, sizeof(t)) != 0) ++ti;
+            const int nb = grid_for((int64_t)a.nphase * a.ntaps * (a.K >> 5) * (a.Nn >> 5) * 128);
+            if (take > 0 && (ti == kBatchTables || blocks + nb > kBatchBlocks)) break;
+            if (ti == ntab) q.table[ntab++] = t;
+            BatchJob& o = q.job[take];
+            o.w = a.w; o.amax = a.amax; o.scale_out = a.scale_out; o.img = a.img;
+            o.sk = a.sk; o.sn = a.sn; o.sr = a.sr; o.ss = a.ss; o.n4 = a.n4;
+            o.K = a.K; o.Nn = a.Nn; o.coef = a.coef; o.bound_mul = a.bound_mul; o.amax_count = a.amax_count; o.table = ti;
+            q.first[take] = blocks;
+            blocks += nb; ++take;
+        }
+        q.first[take] = blocks;
+        q.count = take;
+        if (launch) hipLaunchKernelGGL(conv_weights_batch_kernel, dim3(blocks), dim3(256), 0, st, q);
+        ++*launches;
+        c0 += take;
+    }
+    return launch ? (int)hipGetLastError() : WC_OK;
+}
+
+int wc_conv_weights_batch_f32(const wc_conv_weights_job* jobs, int count, wc_stream_t stream)
+{
+    int launches;
+    return weights_batch(jobs, count, true, (hipStream_t)stream, &launches);
+}
+
+int wc_conv_weights_batch_launches(const wc_conv_weights_job* jobs, int count)
+{
+    int launches = 0;
+    const int rc = weights_batch(jobs, count, false, nullptr, &launches);
+    return rc != WC_OK ? rc : launches;
+}
+
+int wc_conv_absmax_batch_f32(const wc_conv_absmax_job* jobs, int count, wc_stream_t stream)
+{
+    if (!jobs) return WC_ERR_NULL;
+    if (count <= 0) return WC_ERR_SHAPE;
+    for (int i = 0; i < count; ++i) {
+        if (!jobs[i].x || !jobs[i].partial) return WC_ERR_NULL;
+        if (jobs[i].n <= 0 || ((uintptr_t)jobs[i].x & 15)) return WC_ERR_ARG;
+    }
+    for (int c0 = 0; c0 < count; c0 += kAbsmaxJobs) {
+        AbsmaxBatch q;
+        memset(&q, 0, sizeof(q));
+        const int take = count - c0 < kAbsmaxJobs ? count - c0 : kAbsmaxJobs;
+        for (int i = 0; i < take; ++i) q.job[i] = AbsmaxJob{jobs[c0 + i].x, jobs[c0 + i].n, jobs[c0 + i].partial};
+        hipLaunchKernelGGL(conv_absmax_batch_kernel, dim3(take * kAmaxBlocks), dim3(256), 0, (hipStream_t)stream, q);
+    }
     return (int)hipGetLastError();
 }
 

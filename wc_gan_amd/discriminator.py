@@ -154,9 +154,17 @@ class Discriminator(nn.Module):
     def forward(self, x, cls=None):
         from .spectral import prepare_spectral
         prepare_spectral(self)              # all spectral-norm layers' weights in one launch (no-op without any)
-        y = x
-        for blk in self.blocks:
-            y = blk(y, cls)
+        from . import conv as fc
+        batch = torch.is_tensor(x) and x.is_cuda
+        if batch:                           # ... and all the block convolutions' weight images in one (conv.prepare_images)
+            fc.prepare_images(self, fc.pass_key(self, x))
+        try:
+            y = x
+            for blk in self.blocks:
+                y = blk(y, cls)
+        finally:
+            if batch:
+                fc.finish_images(self)
         if self.arch == 'dcgan':
             y = F.leaky_relu(y, LEAKY_SLOPE).flatten(1)
         else:
