@@ -948,6 +948,9 @@ int wc_bwd_xsplit_supported(int64_t N, int64_t HW, int C, int has_slot)
     const XtyPlan p = plan_xty(per_sample ? N : 1, per_sample ? HW : N * HW, C, per_sample, 0);
     if (!p.fast || !wc_fast_affine_supported(N, HW, C, has_slot != 0)) return 0;
     // C = 256: K6 in one pass; C = 128 (round 5): the planes kernel for (x - mu) S - sub, then the accumulating fp32 kernel for + gy At
+    // -- whose 128-row tiles take ONE table each and have no per-row redo: with a slot table every tile must lie inside a sample
+    // (HW = 64, 192, 576 ... would give the second sample of a tile its neighbour's table).  Such a site reads the fp32 copy of x.
+    if (C == 128 && has_slot && (HW % 128) != 0) return 0;
     return (C == 256 ? wc_bwd_apply_onepass_supported(N, HW, C) : wc_split_apply_supported(N, HW, C)) ? 1 : 0;
 }
 

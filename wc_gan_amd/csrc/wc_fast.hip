@@ -1407,6 +1407,9 @@ hipError_t launch_affine(const FastArgs& a, hipStream_t st)
     constexpr int BM = 64 * 256 / C;
     constexpr size_t lds = (size_t)4 * BM * C * 2 + 16;     // 128 KiB of images + the two dirty tags
     FastArgs b = a;
+    // one table per tile and no per-row redo here (affine_ring_kernel and onepass_ring_kernel have one): with a slot table a tile
+    // must not straddle samples
+    if (a.slot != nullptr && (a.HW % BM) != 0) return hipErrorInvalidValue;
     b.ntiles = (int)(a.M / BM);
     int nwg = b.ntiles < 256 ? b.ntiles : 256;
     b.tiles_per_wg = (b.ntiles + nwg - 1) / nwg;
@@ -1439,8 +1442,9 @@ bool wc_fast_affine_supported(int64_t N, int64_t HW, int C, bool has_slot)
     const int64_t M = N * HW;
     if (M < wc_fast_affine_min_rows()) return false;
     const int BM = 64 * 256 / C;
-    // (has_slot adds no condition: the ring kernel, which every non-accumulating call takes, redoes tiles that straddle samples of
-    // different slots)
+    // (has_slot adds no condition HERE: the ring kernel, which every non-accumulating call takes, redoes tiles that straddle samples
+    // of different slots.  The accumulating kernel does not -- launch_affine refuses a slot table with HW % BM != 0 -- and the one
+    // accumulating call that takes per-sample tables, K6 on planes at C = 128, is gated by wc_bwd_xsplit_supported.)
     if ((M % BM) != 0) return false;                         // whole tiles only (keeps the kernel free of masked accesses)
     return true;
 }
