@@ -944,6 +944,30 @@ int wc_adam_capacity(void);       /* WC_ADAM_CAPACITY, for a binding to check it
 int wc_adam_update_f32(const wc_adam_table* table, float* exp_avg /*nullable when beta1 == 0*/, float* exp_avg_sq, int64_t moment_elems,
                        const float* record, double beta1, double beta2, float eps, wc_stream_t stream);
 
+/* ==== the ResNet critic's tail and the AC-GAN class loss (scripts/cifar10_resnet_wgan_cond*.sh, --gan_type AC_GAN), DESIGN.md section 4.19 ====
+ * Additive like the blocks above: WC_CORE_API keeps its list and WC_ABI_VERSION its value.  Stream-ordered and graph-capturable; nothing
+ * allocates or synchronises, no atomics: the same bits on every call.  y [N, HW, C] fp32 NHWC, 16-byte aligned like dy, w_out and w_cls
+ * (WC_ERR_ARG otherwise); s = 1 (sum_pool = 1)
+ * or 1 / HW (sum_pool = 0); K = 0: no class head (w_cls, b_cls, logits, lse, labels, ce NULL).  Sums in float64, each value rounded once.
+ *     feat[n,c]  = s sum_hw relu(y[n,hw,c])        out[n] = feat[n] . w_out + b_out        logits[n,k] = feat[n] . w_cls[k] + b_cls[k]
+ *     lse[n]     = log sum_k exp(logits[n,k])  (the row maximum subtracted)                ce[n] = lse[n] - logits[n, labels[n]]
+ * labels / ce: both or neither; a label outside [0, K) reads nothing, its ce is NaN and its class gradient zero.  b_out, b_cls nullable (0). */
+int wc_critic_tail_supported(int64_t N, int64_t HW, int C, int K);     /* 1 iff N, HW >= 1, 4 <= C <= 1024, C % 4 == 0, 0 <= K <= 1024, N HW C < 2^31 */
+int wc_critic_tail_fwd_f32(const float* y, const float* w_out /*[C]*/, const float* b_out /*[1]*/, const float* w_cls /*[K,C]*/,
+                           const float* b_cls /*[K]*/, const int32_t* labels /*[N], nullable*/, int64_t N, int64_t HW, int C, int K, int sum_pool,
+                           float* feat /*[N,C]*/, float* out /*[N]*/, float* logits /*[N,K]*/, float* lse /*[N]*/, float* ce /*[N], nullable*/,
+                           wc_stream_t stream);
+/*     dlogits[n,k] = g_logits[n,k] + g_ce[n] (exp(logits[n,k] - lse[n]) - 1[k = labels[n]])         (g_logits, g_ce nullable: zero)
+ *     dy[n,hw,c]   = y[n,hw,c] > 0 ? s (g_out[n] w_out[c] + sum_k dlogits[n,k] w_cls[k,c]) : 0
+ * y is read once and dy written once; no expanded gradient and no masked copy exist.  logits, lse, labels: the forward's, read with g_ce. */
+int wc_critic_tail_bwd_f32(const float* y, const float* w_out, const float* w_cls, const float* g_out /*[N]*/, const float* g_logits /*[N,K]*/,
+                           const float* g_ce /*[N]*/, const float* logits, const float* lse, const int32_t* labels, int64_t N, int64_t HW, int C,
+                           int K, int sum_pool, float* dlogits /*[N,K]*/, float* dy /*[N,HW,C]*/, wc_stream_t stream);
+/*     dw_out[c] = sum_n g_out[n] feat[n,c]    db_out = sum_n g_out[n]    dW_cls[k,c] = sum_n dlogits[n,k] feat[n,c]    db_cls[k] = sum_n dlogits[n,k]
+ * summed over n in a fixed order, one thread per weight. */
+int wc_critic_tail_wgrad_f32(const float* feat, const float* g_out, const float* dlogits, int64_t N, int C, int K, float* dw_out /*[C]*/,
+                             float* db_out /*[1]*/, float* dW_cls /*[K,C]*/, float* db_cls /*[K]*/, wc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,12 @@ SIGNATURES = {
     "wc_adam_capacity": (c_int, []),
     "wc_adam_tick": (c_int, [c_void_p, c_void_p, c_double, c_double, c_double, c_int, c_double, c_double, c_void_p]),
     "wc_adam_update_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_double, c_double, c_float, c_void_p]),
+    "wc_critic_tail_supported": (c_int, [c_int64, c_int64, c_int, c_int]),
+    "wc_critic_tail_fwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wc_critic_tail_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "wc_critic_tail_wgrad_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 ADAM_CAPACITY = 96       # WC_ADAM_CAPACITY

@@ -117,8 +117,11 @@ class DCBlockDown(nn.Module):
 
 class Discriminator(nn.Module):
     def __init__(self, in_ch, block_sizes, resamples, norm_layer, conv_layer, dense, emb, number_of_classes, type,
-                 sum_pool, dropout, arch='res', input_hw=None):
+                 sum_pool, dropout, arch='res', input_hw=None, fused_tail=False):
         super().__init__()
+        # fused_tail: ReLU -> pooling -> heads (-> cross entropy) as the one autograd node of tail.critic_tail where
+        # that covers the critic: arch='res', no dropout, type None or 'AC_GAN'.  Off by default: every other recipe keeps the torch tail
+        self.fused_tail = bool(fused_tail)
         blocks = []
         ch = in_ch
         self.arch = arch
@@ -151,7 +154,14 @@ class Discriminator(nn.Module):
         elif type == 'PROJECTIVE':
             self.emb = emb(number_of_classes, emb_dim)
 
-    def forward(self, x, cls=None):
+    def _tail_is_fused(self):
+        return self.fused_tail and self.arch == 'res' and self.dropout is None and self.type in (None, 'AC_GAN')
+
+    def forward(self, x, cls=None, labels=None):
+        """labels (type='AC_GAN' only): the class of each sample, (N,) or (N, 1) integers -- the call then returns (out, logits, ce) with
+        ce[n] the cross entropy of logits[n] against labels[n]; without labels it returns what it always did."""
+        if labels is not None and self.type != 'AC_GAN':
+            raise ValueError("Discriminator.forward: labels are the AC_GAN class head's; this critic has type " + repr(self.type))
         from .spectral import prepare_spectral
         prepare_spectral(self)              # all spectral-norm layers' weights in one launch (no-op without any)
         from . import conv as fc
@@ -165,6 +175,15 @@ class Discriminator(nn.Module):
         finally:
             if batch:
                 fc.finish_images(self)
+        if self._tail_is_fused():
+            from .tail import critic_tail
+            w_out = self.out.normalized_weight() if hasattr(self.out, 'normalized_weight') else self.out.weight
+            ac = self.type == 'AC_GAN'
+            out, logits, ce = critic_tail(y, w_out, self.out.bias, self.cls_out.weight if ac else None, self.cls_out.bias if ac else None,
+                                          labels, self.sum_pool)
+            if not ac:
+                return out
+            return (out, logits) if labels is None else (out, logits, ce)
         if self.arch == 'dcgan':
             y = F.leaky_relu(y, LEAKY_SLOPE).flatten(1)
         else:
@@ -174,7 +193,10 @@ class Discriminator(nn.Module):
             y = self.dropout(y)
         out = self.out(y)
         if self.type == 'AC_GAN':
-            return out, self.cls_out(y)
+            logits = self.cls_out(y)
+            if labels is None:
+                return out, logits
+            return out, logits, F.cross_entropy(logits, labels.reshape(-1).long(), reduction='none')
         if self.type == 'PROJECTIVE':
             out = out + (self.emb(cls.reshape(-1).long()) * y).sum(dim=1, keepdim=True)
         return out
@@ -184,12 +206,12 @@ def make_discriminator(input_image_shape=(32, 32, 3), input_cls_shape=(1,), bloc
                        resamples=('DOWN', 'DOWN', 'SAME', 'SAME'), number_of_classes=10,
                        type='AC_GAN', norm='n', after_norm='n', spectral=False,
                        fully_diff_spectral=False, spectral_iterations=1, conv_singular=True,
-                       sum_pool=False, dropout=False, arch='res', filters_emb=10):
+                       sum_pool=False, dropout=False, arch='res', filters_emb=10, fused_tail=False):
     """Keyword surface AND defaults of discriminator.py:15-20.  The shipped recipes pass type / spectral / sum_pool
     explicitly (run.py:230-233 from --gan_type, --discriminator_spectral, --sum_pool default 1), as wc_gan_amd.train's
     configs do.  `conv_singular=True` (the reference's default here; run.py:270 passes 0) asks for the
     convolution-operator singular value of SNConv2D, which this harness does not build: it warns and uses the
-    reshaped-kernel sigma of the SN-GAN paper."""
+    reshaped-kernel sigma of the SN-GAN paper.  `fused_tail` (ours, default False): see Discriminator."""
     assert arch in ('res', 'dcgan')
     assert type in [None, 'AC_GAN', 'PROJECTIVE']
     if spectral and conv_singular:
@@ -219,4 +241,4 @@ def make_discriminator(input_image_shape=(32, 32, 3), input_cls_shape=(1,), bloc
 
     norm_layer = create_norm(norm, after_norm, number_of_classes=number_of_classes, filters_emb=filters_emb)
     return Discriminator(int(input_image_shape[-1]), block_sizes, resamples, norm_layer, conv_layer, dense, emb,
-                         number_of_classes, type, sum_pool, dropout, arch=arch, input_hw=input_image_shape[:2])
+                         number_of_classes, type, sum_pool, dropout, arch=arch, input_hw=input_image_shape[:2], fused_tail=fused_tail)

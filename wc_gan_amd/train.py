@@ -123,7 +123,22 @@ class GanTrainer:
                  lr=2e-4, beta1=0.0, beta2=0.9, noise_dim=128, number_of_classes=10, conditional=False,
                  process_group=None, seed=1234, flat_buckets=None, objective='hinge', gradient_penalty_weight=0.0,
                  lr_decay_schedule=None, number_of_epochs=None, schedule_iters=None, generator_lr=None, discriminator_lr=None,
-                 optimizer=None):
+                 optimizer=None, gan_type=None, class_loss_weight_discriminator=1.0, class_loss_weight_generator=1.0):
+        if gan_type not in (None, 'AC_GAN'):
+            raise ValueError(f"gan_type {gan_type!r}: None or 'AC_GAN' (a PROJECTIVE recipe is `conditional=True` with a PROJECTIVE critic)")
+        # 'AC_GAN' (scripts/cifar10_resnet_wgan_cond*.sh, run.py --gan_type AC_GAN): the critic's class head is trained with a cross entropy
+        # beside the adversarial loss, and the generator is asked for samples the head assigns to the classes it drew.  gan/ac_gan.py is not
+        # in the reference tree, so THESE CONVENTIONS ARE OURS AND UNPINNED: the critic's class loss is
+        # w_d (mean ce(real) + mean ce(generated)) -- both halves --, the generator's w_g mean ce(generated), both weights 1.  The critic
+        # takes no label input (`conditional` stays False) and the gradient penalty stays on the adversarial head.
+        self.gan_type = gan_type
+        self.w_cls_d, self.w_cls_g = float(class_loss_weight_discriminator), float(class_loss_weight_generator)
+        self.last_class_losses = [None, None, None]     # device scalars: mean ce of the real half, of the generated half, of the generator's batch
+        if gan_type == 'AC_GAN':
+            if getattr(discriminator, 'type', None) != 'AC_GAN':
+                raise ValueError("gan_type='AC_GAN' needs a critic with the class head (make_discriminator(type='AC_GAN'))")
+            if conditional:
+                raise ValueError("gan_type='AC_GAN': the critic takes no label input (conditional=False)")
         if objective not in ('hinge', 'wgan'):
             raise ValueError(f"objective {objective!r}: 'hinge' or 'wgan' (run.py --*_adversarial_objective)")
         # 'wgan' (scripts/cifar10_resnet_wgan_*.sh): the critic loss E D(fake) - E D(real), plus gradient_penalty_weight x the gradient
@@ -188,6 +203,11 @@ class GanTrainer:
         out = self.D(x, cls if self.conditional else None)
         return out[0] if isinstance(out, tuple) else out
 
+    def _adv_loss_d(self, out, n):
+        if self.objective == 'wgan':
+            return out[n:].mean() - out[:n].mean()
+        return F.relu(1.0 - out[:n]).mean() + F.relu(1.0 + out[n:]).mean()
+
     def generate(self, rounds):
         """The `rounds` generated batches of one G+D step in ONE generator pass.  The generator's weights are fixed
         while the critic trains, so its `rounds` forward passes are independent; they run as a single batch of
@@ -219,11 +239,16 @@ class GanTrainer:
             both_cls = torch.cat([real_cls.reshape(-1, 1).to(cls.dtype), cls], dim=0)
         else:
             both_cls = None
-        out = self._d(torch.cat([real, fake], dim=0), both_cls)
-        if self.objective == 'wgan':
-            loss = out[n:].mean() - out[:n].mean()
+        if self.gan_type == 'AC_GAN':
+            if real_cls is None:
+                raise ValueError("gan_type='AC_GAN': d_step needs the labels of the real batch (real_cls)")
+            labels = torch.cat([real_cls.reshape(-1).to(cls.dtype), cls.reshape(-1)], dim=0)
+            out, _logits, ce = self.D(torch.cat([real, fake], dim=0), None, labels=labels)
+            ce_real, ce_fake = ce[:n].mean(), ce[n:].mean()
+            self.last_class_losses[0], self.last_class_losses[1] = ce_real.detach(), ce_fake.detach()
+            loss = self._adv_loss_d(out, n) + self.w_cls_d * (ce_real + ce_fake)
         else:
-            loss = F.relu(1.0 - out[:n]).mean() + F.relu(1.0 + out[n:]).mean()
+            loss = self._adv_loss_d(self._d(torch.cat([real, fake], dim=0), both_cls), n)
         loss.backward()
         loss = loss.detach()
         if self.gp_weight != 0.0:
@@ -247,7 +272,13 @@ class GanTrainer:
             fake, cls = generated
         for p in self.d_bucket.params:
             p.requires_grad_(False)
-        loss = -self._d(fake, cls).mean()
+        if self.gan_type == 'AC_GAN':
+            out, _logits, ce = self.D(fake, None, labels=cls.reshape(-1))
+            ce_g = ce.mean()
+            self.last_class_losses[2] = ce_g.detach()
+            loss = -out.mean() + self.w_cls_g * ce_g
+        else:
+            loss = -self._d(fake, cls).mean()
         loss.backward()
         for p in self.d_bucket.params:
             p.requires_grad_(True)
@@ -259,9 +290,11 @@ class GanTrainer:
     def step(self, real_batches, real_labels=None):
         """One G+D step: training_ratio critic updates, then one generator update.  `real_labels`: one int (64,) or
         (64, 1) tensor per real batch -- required by the conditional recipes (the projection critic must see true
-        (image, label) pairs; run.py:317)."""
+        (image, label) pairs; run.py:317) and by gan_type='AC_GAN' (the class head learns from them)."""
         if self.conditional and real_labels is None:
             raise ValueError("conditional recipe: step() needs real_labels (one label tensor per real batch)")
+        if self.gan_type == 'AC_GAN' and real_labels is None:
+            raise ValueError("gan_type='AC_GAN': step() needs real_labels (one label tensor per real batch): the class head learns from them")
         fakes, clss = self.generate(self.training_ratio)
         generated = None
         if self.overlap_g_forward and self.dev.type == 'cuda':
@@ -480,13 +513,35 @@ DCGAN_CONFIGS = {'cifar10_dcgan_uncond': _dcgan(4, (32, 32, 3)), 'stl10_dcgan_un
 
 # scripts/cifar10_resnet_wgan_uncond.sh: --generator_adversarial_objective wgan --discriminator_adversarial_objective wgan
 # --gradinet_penalty_weight 10, generator_filters = discriminator_filters = 128, norms d / uconv, no spectral normalisation, critic norm 'n'.
-# NOT in CONFIGS either.  (The two conditional WGAN scripts use an AC_GAN critic, whose classification loss no recipe here trains yet.)
+# NOT in CONFIGS either.  (The two conditional WGAN scripts: ACGAN_CONFIGS below.)
 WGAN_CONFIGS = {'cifar10_wgan_uncond': dict(
     generator=dict(block_sizes=(128, 128, 128), resamples=("UP", "UP", "UP"), first_block_shape=(4, 4, 128),
                    number_of_classes=10, block_norm='d', block_after_norm='uconv', last_norm='d', last_after_norm='uconv', gan_type=None),
     discriminator=dict(input_image_shape=(32, 32, 3), block_sizes=(128, 128, 128, 128), resamples=('DOWN', 'DOWN', 'SAME', 'SAME'),
                        number_of_classes=10, type=None, spectral=False, sum_pool=True),
     image_shape=(32, 32, 3), conditional=False, objective='wgan', gradient_penalty_weight=10)}
+
+
+def _wgan_cond(after_norm, filters_emb=None):
+    """scripts/cifar10_resnet_wgan_cond.sh (ucconv) and scripts/cifar10_resnet_wgan_cond_sa.sh (ufconv, --filters_emb 4): --gan_type AC_GAN,
+    wgan objectives, --gradinet_penalty_weight 10, generator_filters = discriminator_filters = 128, norms d / uconv at the last site, no
+    spectral normalisation, critic norm 'n', --sum_pool 1.  The critic takes no label input (conditional=False): its class head is trained by
+    GanTrainer(gan_type='AC_GAN') on the fused tail (tail.py)."""
+    emb = {} if filters_emb is None else dict(filters_emb=filters_emb)
+    return dict(
+        generator=dict(block_sizes=(128, 128, 128), resamples=("UP", "UP", "UP"), first_block_shape=(4, 4, 128), number_of_classes=10,
+                       block_norm='d', block_after_norm=after_norm, last_norm='d', last_after_norm='uconv', gan_type='AC_GAN', **emb),
+        discriminator=dict(input_image_shape=(32, 32, 3), block_sizes=(128, 128, 128, 128), resamples=('DOWN', 'DOWN', 'SAME', 'SAME'),
+                           number_of_classes=10, type='AC_GAN', spectral=False, sum_pool=True, fused_tail=True, **emb),
+        image_shape=(32, 32, 3), conditional=False, objective='wgan', gradient_penalty_weight=10, gan_type='AC_GAN')
+
+
+# the two conditional WGAN-GP recipes (the paper's cWC and cWC-sa rows); NOT in CONFIGS, and their schedules in a table of their own
+ACGAN_CONFIGS = {'cifar10_wgan_cond': _wgan_cond('ucconv'), 'cifar10_wgan_cond_sa': _wgan_cond('ufconv', filters_emb=4)}
+ACGAN_SCHEDULES = {
+    'cifar10_wgan_cond': dict(lr_decay_schedule='linear', number_of_epochs=100),        # scripts/cifar10_resnet_wgan_cond.sh:7
+    'cifar10_wgan_cond_sa': dict(lr_decay_schedule='linear', number_of_epochs=100),     # scripts/cifar10_resnet_wgan_cond_sa.sh:7
+}
 
 
 # --lr_decay_schedule / --number_of_epochs of each recipe's script: GanTrainer's arguments of the same names (the config tables above carry
@@ -571,7 +626,7 @@ def build_trainer(config=CIFAR10_UNCOND, device='cuda', process_group=None, sync
     broadcast_state(G, group=process_group)
     broadcast_state(D, group=process_group)
     # a recipe's own schedule (DCGAN_CONFIGS) and objective (WGAN_CONFIGS), unless the caller overrides them
-    for key in ('training_ratio', 'generator_batch_multiple', 'objective', 'gradient_penalty_weight'):
+    for key in ('training_ratio', 'generator_batch_multiple', 'objective', 'gradient_penalty_weight', 'gan_type'):
         if key in config:
             kw.setdefault(key, config[key])
     return GanTrainer(G, D, number_of_classes=config['generator']['number_of_classes'],
