@@ -968,6 +968,23 @@ int wc_critic_tail_bwd_f32(const float* y, const float* w_out, const float* w_cl
 int wc_critic_tail_wgrad_f32(const float* feat, const float* g_out, const float* dlogits, int64_t N, int C, int K, float* dw_out /*[C]*/,
                              float* db_out /*[1]*/, float* dW_cls /*[K,C]*/, float* db_cls /*[K]*/, wc_stream_t stream);
 
+/* ==== the projection critic's tail (--gan_type PROJECTIVE: out = psi(f) + <emb[cls], f>, discriminator.py:77-82), DESIGN.md section 4.20 ====
+ * Additive again: WC_CORE_API and WC_ABI_VERSION stay.  The rules of the block above; emb [K, C] is whatever table the caller holds (the
+ * spectral-norm op's output or the Embedding's weight), 16-byte aligned like y, dy and w_out (WC_ERR_ARG otherwise); cls [N] int32.
+ *     feat[n,c] = s sum_hw relu(y[n,hw,c])                     out[n] = feat[n] . (w_out + emb[cls[n]]) + b_out           (b_out nullable: 0)
+ *     dy[n,hw,c] = y[n,hw,c] > 0 ? s g_out[n] (w_out[c] + emb[cls[n],c]) : 0
+ *     dw_out[c] = sum_n g_out[n] feat[n,c]    db_out = sum_n g_out[n]    demb[k,c] = sum_{n : cls[n] = k} g_out[n] feat[n,c]
+ * demb is dense and written in full, ascending n within a row; the row of a class no sample carries is exactly 0.  A label outside [0, K)
+ * reads nothing: its out is NaN, its dy carries the w_out term alone and it adds to no row of demb. */
+int wc_critic_proj_supported(int64_t N, int64_t HW, int C, int K);     /* wc_critic_tail_supported's limits with K >= 1 */
+int wc_critic_proj_fwd_f32(const float* y, const float* w_out /*[C]*/, const float* b_out /*[1]*/, const float* emb /*[K,C]*/,
+                           const int32_t* cls /*[N]*/, int64_t N, int64_t HW, int C, int K, int sum_pool, float* feat /*[N,C]*/,
+                           float* out /*[N]*/, wc_stream_t stream);
+int wc_critic_proj_bwd_f32(const float* y, const float* w_out, const float* emb, const int32_t* cls, const float* g_out /*[N]*/, int64_t N,
+                           int64_t HW, int C, int K, int sum_pool, float* dy /*[N,HW,C]*/, wc_stream_t stream);
+int wc_critic_proj_wgrad_f32(const float* feat, const float* g_out, const int32_t* cls, int64_t N, int C, int K, float* dw_out /*[C]*/,
+                             float* db_out /*[1]*/, float* demb /*[K,C]*/, wc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

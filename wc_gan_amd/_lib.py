@@ -214,6 +214,11 @@ SIGNATURES = {
     "wc_critic_tail_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "wc_critic_tail_wgrad_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wc_critic_proj_supported": (c_int, [c_int64, c_int64, c_int, c_int]),
+    "wc_critic_proj_fwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int,
+                                       c_void_p, c_void_p, c_void_p]),
+    "wc_critic_proj_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "wc_critic_proj_wgrad_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 ADAM_CAPACITY = 96       # WC_ADAM_CAPACITY

@@ -1,5 +1,5 @@
 // The tail of a ResNet critic (discriminator.py:57-85 of the reference: ReLU -> global pooling -> Dense heads) and the AC-GAN class loss
-// as three launches -- DESIGN.md section 4.19.  For y [N, HW, C] fp32 NHWC:
+// as three launches -- DESIGN.md section 4.19; the projection head's three further down (section 4.20).  For y [N, HW, C] fp32 NHWC:
 //
 //   f[n,c]     = s sum_hw relu(y[n,hw,c])                       s = 1 (sum pooling) or 1 / HW (mean pooling)
 //   out[n]     = f[n] . w_out + b_out
@@ -246,6 +246,128 @@ __global__ __launch_bounds__(kWgradThreads) void tail_wgrad_kernel(const float* 
     }
 }
 
+// ---- the projection head (discriminator.py:77-82 of the reference: out = psi(f) + <emb[cls], f>), DESIGN.md section 4.20 ----
+//
+//   out[n]     = f[n] . (w_out + E[cls[n]]) + b_out
+//   dy[n,hw,c] = y[n,hw,c] > 0 ? s g_out[n] (w_out[c] + E[cls[n],c]) : 0
+//   dE[k,c]    = sum_{n : cls[n] = k} g_out[n] f[n,c]            (ascending n; a class no sample carries: exactly 0)
+//
+// The pooling is tail_fwd_kernel's, sum for sum; a label outside [0, K) reads no row of E: its out is NaN, its dy the adversarial head's alone.
+__global__ __launch_bounds__(kThreads) void proj_fwd_kernel(const float* __restrict__ y, const float* __restrict__ w_out, const float* __restrict__ b_out,
+                                                            const float* __restrict__ emb, const int32_t* __restrict__ cls, int64_t HW, int C, int K,
+                                                            double s, float* __restrict__ feat, float* __restrict__ out)
+{
+    __shared__ double part[4 * kMaxC];      // [R][C]: R * C4 <= 1024
+    __shared__ __attribute__((aligned(16))) float f[kMaxC];
+    __shared__ double wp[kWaves];
+    const int64_t n = blockIdx.x;
+    const int tid = threadIdx.x, C4 = C >> 2, R = min(kThreads / C4, kMaxParts);
+    if (tid < R * C4) {
+        const int c4 = tid % C4, r = tid / C4;
+        const float* col = y + n * HW * C + 4 * c4;
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int64_t hw = r; hw < HW; hw += R) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(col + hw * C);
+            #pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] += v[j] > 0.f ? (double)v[j] : 0.0;
+        }
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) part[r * C + 4 * c4 + j] = acc[j];
+    }
+    __syncthreads();
+    for (int c = tid; c < C; c += kThreads) {
+        double t = 0.0;
+        for (int r = 0; r < R; ++r) t += part[r * C + c];
+        const float v = (float)(s * t);
+        f[c] = v;
+        feat[n * C + c] = v;
+    }
+    __syncthreads();
+    // thread t < C4 takes the channels 4 t .. 4 t + 3 of both rows; the (at most four) waves' sums are folded in order
+    const int32_t k = cls[n];
+    const bool valid = k >= 0 && k < K;
+    const int lane = tid & 63, wave = tid >> 6, nw = (C4 + 63) >> 6;
+    if (wave < nw) {
+        double a = 0.0;
+        if (tid < C4) {
+            const f32x4 fv = *reinterpret_cast<const f32x4*>(f + 4 * tid);
+            a = dot4(a, fv, *reinterpret_cast<const f32x4*>(w_out + 4 * tid));
+            if (valid) a = dot4(a, fv, *reinterpret_cast<const f32x4*>(emb + (int64_t)k * C + 4 * tid));
+        }
+        a = wave_sum(a);
+        if (lane == 0) wp[wave] = a;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double t = 0.0;
+        for (int w = 0; w < nw; ++w) t += wp[w];
+        out[n] = valid ? (float)(t + (b_out ? (double)b_out[0] : 0.0)) : __builtin_nanf("");
+    }
+}
+
+// thread t < R * C4 (R = 1024 / C4) forms the coefficient of its four channels itself: no LDS
+__global__ __launch_bounds__(kThreads) void proj_bwd_kernel(const float* __restrict__ y, const float* __restrict__ w_out, const float* __restrict__ emb,
+                                                            const int32_t* __restrict__ cls, const float* __restrict__ g_out, int64_t HW, int C, int K,
+                                                            double s, float* __restrict__ dy)
+{
+    const int64_t n = blockIdx.x;
+    const int tid = threadIdx.x, C4 = C >> 2, R = kThreads / C4;
+    if (tid >= R * C4) return;
+    const int c4 = tid % C4, r = tid / C4;
+    const int32_t k = cls[n];
+    const double sg = s * (double)g_out[n];
+    const f32x4 w = *reinterpret_cast<const f32x4*>(w_out + 4 * c4);
+    f32x4 e = {0.f, 0.f, 0.f, 0.f};
+    if (k >= 0 && k < K) e = *reinterpret_cast<const f32x4*>(emb + (int64_t)k * C + 4 * c4);
+    f32x4 cf;
+    #pragma unroll
+    for (int j = 0; j < 4; ++j) cf[j] = (float)(sg * ((double)w[j] + (double)e[j]));
+    const int64_t base = n * HW * C + 4 * c4;
+    for (int64_t hw = r; hw < HW; hw += R) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(y + base + hw * C);
+        f32x4 d;
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) d[j] = v[j] > 0.f ? cf[j] : 0.f;
+        *reinterpret_cast<f32x4*>(dy + base + hw * C) = d;
+    }
+}
+
+// blockIdx.x = the row (k < K: the table's, K: the adversarial head's), blockIdx.y = a block of 256 channels; one thread per weight, the
+// samples in order.  A table row takes the samples of its class -- the test is the same for every thread --, so every row is written in full.
+__global__ __launch_bounds__(kWgradThreads) void proj_wgrad_kernel(const float* __restrict__ feat, const float* __restrict__ g_out,
+                                                                   const int32_t* __restrict__ cls, int64_t N, int C, int K,
+                                                                   float* __restrict__ dw_out, float* __restrict__ db_out, float* __restrict__ demb)
+{
+    const int k = blockIdx.x, c = blockIdx.y * kWgradThreads + threadIdx.x;
+    if (k < K) {
+        if (c >= C) return;
+        double a = 0.0;
+        for (int64_t n = 0; n < N; ++n)
+            if (cls[n] == k) a += (double)g_out[n] * (double)feat[n * C + c];
+        demb[(int64_t)k * C + c] = (float)a;
+        return;
+    }
+    if (c < C) {
+        double a = 0.0;
+        int64_t n = 0;
+        for (; n + 8 <= N; n += 8) {
+            float fv[8], gv[8];
+            #pragma unroll
+            for (int u = 0; u < 8; ++u) { fv[u] = feat[(n + u) * C + c]; gv[u] = g_out[n + u]; }
+            #pragma unroll
+            for (int u = 0; u < 8; ++u) a += (double)gv[u] * (double)fv[u];
+        }
+        for (; n < N; ++n) a += (double)g_out[n] * (double)feat[n * C + c];
+        dw_out[c] = (float)a;
+    }
+    if (blockIdx.y == 0 && threadIdx.x < 64) {      // the bias: lane-strided partial sums folded in a fixed order
+        double b = 0.0;
+        for (int64_t n = threadIdx.x; n < N; n += 64) b += (double)g_out[n];
+        b = wave_sum(b);
+        if (threadIdx.x == 0) db_out[0] = (float)b;
+    }
+}
+
 }  // namespace
 
 static bool misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }      // y, dy and the heads' weights are read 16 bytes at a time
@@ -300,6 +422,42 @@ int wc_critic_tail_wgrad_f32(const float* feat, const float* g_out, const float*
     if (K > 0 && (!dlogits || !dW_cls || !db_cls)) return WC_ERR_NULL;
     hipLaunchKernelGGL(tail_wgrad_kernel, dim3((unsigned)(K + 1), (unsigned)((C + kWgradThreads - 1) / kWgradThreads)), dim3(kWgradThreads), 0,
                        (hipStream_t)stream, feat, g_out, dlogits, N, C, K, dw_out, db_out, dW_cls, db_cls);
+    return (int)hipGetLastError();
+}
+
+int wc_critic_proj_supported(int64_t N, int64_t HW, int C, int K) { return K >= 1 && wc_critic_tail_supported(N, HW, C, K); }
+
+int wc_critic_proj_fwd_f32(const float* y, const float* w_out, const float* b_out, const float* emb, const int32_t* cls, int64_t N, int64_t HW, int C,
+                           int K, int sum_pool, float* feat, float* out, wc_stream_t stream)
+{
+    if (sum_pool != 0 && sum_pool != 1) return WC_ERR_ARG;
+    if (!wc_critic_proj_supported(N, HW, C, K)) return WC_ERR_SHAPE;
+    if (!y || !w_out || !emb || !cls || !feat || !out) return WC_ERR_NULL;
+    if (misaligned(y) || misaligned(w_out) || misaligned(emb)) return WC_ERR_ARG;
+    hipLaunchKernelGGL(proj_fwd_kernel, dim3((unsigned)N), dim3(kThreads), 0, (hipStream_t)stream, y, w_out, b_out, emb, cls, HW, C, K,
+                       sum_pool ? 1.0 : 1.0 / (double)HW, feat, out);
+    return (int)hipGetLastError();
+}
+
+int wc_critic_proj_bwd_f32(const float* y, const float* w_out, const float* emb, const int32_t* cls, const float* g_out, int64_t N, int64_t HW, int C,
+                           int K, int sum_pool, float* dy, wc_stream_t stream)
+{
+    if (sum_pool != 0 && sum_pool != 1) return WC_ERR_ARG;
+    if (!wc_critic_proj_supported(N, HW, C, K)) return WC_ERR_SHAPE;
+    if (!y || !w_out || !emb || !cls || !g_out || !dy) return WC_ERR_NULL;
+    if (misaligned(y) || misaligned(dy) || misaligned(w_out) || misaligned(emb)) return WC_ERR_ARG;
+    hipLaunchKernelGGL(proj_bwd_kernel, dim3((unsigned)N), dim3(kThreads), 0, (hipStream_t)stream, y, w_out, emb, cls, g_out, HW, C, K,
+                       sum_pool ? 1.0 : 1.0 / (double)HW, dy);
+    return (int)hipGetLastError();
+}
+
+int wc_critic_proj_wgrad_f32(const float* feat, const float* g_out, const int32_t* cls, int64_t N, int C, int K, float* dw_out, float* db_out,
+                             float* demb, wc_stream_t stream)
+{
+    if (!wc_critic_proj_supported(N, 1, C, K)) return WC_ERR_SHAPE;
+    if (!feat || !g_out || !cls || !dw_out || !db_out || !demb) return WC_ERR_NULL;
+    hipLaunchKernelGGL(proj_wgrad_kernel, dim3((unsigned)(K + 1), (unsigned)((C + kWgradThreads - 1) / kWgradThreads)), dim3(kWgradThreads), 0,
+                       (hipStream_t)stream, feat, g_out, cls, N, C, K, dw_out, db_out, demb);
     return (int)hipGetLastError();
 }
 

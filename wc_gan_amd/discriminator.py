@@ -117,11 +117,13 @@ class DCBlockDown(nn.Module):
 
 class Discriminator(nn.Module):
     def __init__(self, in_ch, block_sizes, resamples, norm_layer, conv_layer, dense, emb, number_of_classes, type,
-                 sum_pool, dropout, arch='res', input_hw=None, fused_tail=False):
+                 sum_pool, dropout, arch='res', input_hw=None, fused_tail=False, fused_projection=False):
         super().__init__()
         # fused_tail: ReLU -> pooling -> heads (-> cross entropy) as the one autograd node of tail.critic_tail where
         # that covers the critic: arch='res', no dropout, type None or 'AC_GAN'.  Off by default: every other recipe keeps the torch tail
         self.fused_tail = bool(fused_tail)
+        # fused_projection: the same for type 'PROJECTIVE' -- tail.projection_tail; a switch of its own, off by default
+        self.fused_projection = bool(fused_projection)
         blocks = []
         ch = in_ch
         self.arch = arch
@@ -157,6 +159,9 @@ class Discriminator(nn.Module):
     def _tail_is_fused(self):
         return self.fused_tail and self.arch == 'res' and self.dropout is None and self.type in (None, 'AC_GAN')
 
+    def _projection_is_fused(self):
+        return self.fused_projection and self.arch == 'res' and self.dropout is None and self.type == 'PROJECTIVE'
+
     def forward(self, x, cls=None, labels=None):
         """labels (type='AC_GAN' only): the class of each sample, (N,) or (N, 1) integers -- the call then returns (out, logits, ce) with
         ce[n] the cross entropy of logits[n] against labels[n]; without labels it returns what it always did."""
@@ -184,6 +189,11 @@ class Discriminator(nn.Module):
             if not ac:
                 return out
             return (out, logits) if labels is None else (out, logits, ce)
+        if self._projection_is_fused():
+            from .tail import projection_tail
+            w_out = self.out.normalized_weight() if hasattr(self.out, 'normalized_weight') else self.out.weight
+            table = self.emb.normalized_weight() if hasattr(self.emb, 'normalized_weight') else self.emb.weight
+            return projection_tail(y, w_out, self.out.bias, table, cls, self.sum_pool)
         if self.arch == 'dcgan':
             y = F.leaky_relu(y, LEAKY_SLOPE).flatten(1)
         else:
@@ -206,12 +216,12 @@ def make_discriminator(input_image_shape=(32, 32, 3), input_cls_shape=(1,), bloc
                        resamples=('DOWN', 'DOWN', 'SAME', 'SAME'), number_of_classes=10,
                        type='AC_GAN', norm='n', after_norm='n', spectral=False,
                        fully_diff_spectral=False, spectral_iterations=1, conv_singular=True,
-                       sum_pool=False, dropout=False, arch='res', filters_emb=10, fused_tail=False):
+                       sum_pool=False, dropout=False, arch='res', filters_emb=10, fused_tail=False, fused_projection=False):
     """Keyword surface AND defaults of discriminator.py:15-20.  The shipped recipes pass type / spectral / sum_pool
     explicitly (run.py:230-233 from --gan_type, --discriminator_spectral, --sum_pool default 1), as wc_gan_amd.train's
     configs do.  `conv_singular=True` (the reference's default here; run.py:270 passes 0) asks for the
     convolution-operator singular value of SNConv2D, which this harness does not build: it warns and uses the
-    reshaped-kernel sigma of the SN-GAN paper.  `fused_tail` (ours, default False): see Discriminator."""
+    reshaped-kernel sigma of the SN-GAN paper.  `fused_tail`, `fused_projection` (ours, default False): see Discriminator."""
     assert arch in ('res', 'dcgan')
     assert type in [None, 'AC_GAN', 'PROJECTIVE']
     if spectral and conv_singular:
@@ -241,4 +251,5 @@ def make_discriminator(input_image_shape=(32, 32, 3), input_cls_shape=(1,), bloc
 
     norm_layer = create_norm(norm, after_norm, number_of_classes=number_of_classes, filters_emb=filters_emb)
     return Discriminator(int(input_image_shape[-1]), block_sizes, resamples, norm_layer, conv_layer, dense, emb,
-                         number_of_classes, type, sum_pool, dropout, arch=arch, input_hw=input_image_shape[:2], fused_tail=fused_tail)
+                         number_of_classes, type, sum_pool, dropout, arch=arch, input_hw=input_image_shape[:2], fused_tail=fused_tail,
+                         fused_projection=fused_projection)

@@ -11,6 +11,13 @@ gradients sums over n of dlogits (or g_out) times f.  One launch forward, two ba
 
 On a CPU tensor, in float64, or for a shape wc_critic_tail_supported turns down, the same map runs in torch ops (`torch_tail`): the form
 the float64 tests compare against, as in penalty.py.
+
+The projection head (`projection_tail`) is a second node over three entries of its own:
+
+    out[n] = f[n] . (w_out + E[cls[n]]) + b_out
+
+with dy = 1[y > 0] s g_out (w_out + E[cls]), dw_out = g_out^T f and the dense dE[k] = sum over the samples of class k, in order, of
+g_out[n] f[n].  A label outside [0, K) gives a NaN out, drops E from that sample's dy and reaches no row of dE.
 """
 from __future__ import annotations
 
@@ -152,3 +159,100 @@ def critic_tail(y, w_out, b_out, w_cls=None, b_cls=None, labels=None, sum_pool=T
         return _CriticTail.apply(y, w_out, b_out, w_cls, b_cls, labels, bool(sum_pool))
     last_route = 'torch'
     return torch_tail(y, w_out, b_out, w_cls, b_cls, labels, sum_pool)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the projection head
+# ---------------------------------------------------------------------------------------------------------------------------------
+def torch_projection_tail(y, w_out, b_out, emb, cls, sum_pool=True):
+    f = F.relu(y)
+    f = f.sum(dim=(1, 2)) if sum_pool else f.mean(dim=(1, 2))
+    out = F.linear(f, w_out.reshape(1, -1), b_out)
+    K = emb.shape[0]
+    idx = cls.reshape(-1).long()
+    valid = ((idx >= 0) & (idx < K))[:, None]
+    rows = torch.where(valid, F.embedding(idx.clamp(0, K - 1), emb), torch.zeros((), dtype=emb.dtype, device=emb.device))
+    out = out + (rows * f).sum(dim=1, keepdim=True)
+    # the kernel's contract: NaN for a label outside [0, K), whose gradient still reaches y, w_out and b_out through the adversarial head
+    return out + torch.where(valid, torch.zeros_like(out), torch.full_like(out, float('nan'))).detach()
+
+
+def hip_projection_forward(y, w_out, b_out, emb, cls, sum_pool=True):
+    """wc_critic_proj_fwd_f32 on dense fp32 tensors: y (N, H, W, C), w_out (C,), emb (K, C), cls int32 (N,) -> (feat (N, C), out (N, 1))"""
+    N, H, W, C = y.shape
+    feat = torch.empty(N, C, dtype=torch.float32, device=y.device)
+    out = torch.empty(N, 1, dtype=torch.float32, device=y.device)
+    _lib.check(_lib.load().wc_critic_proj_fwd_f32(_ptr(y), _ptr(w_out), _ptr(b_out), _ptr(emb), _ptr(cls), N, H * W, C, emb.shape[0],
+                                                  int(bool(sum_pool)), _ptr(feat), _ptr(out), _stream()), "wc_critic_proj_fwd_f32")
+    return feat, out
+
+
+def hip_projection_backward(y, w_out, emb, cls, g_out, sum_pool=True):
+    """wc_critic_proj_bwd_f32: g_out (N,) -> dy"""
+    N, H, W, C = y.shape
+    dy = torch.empty_like(y)
+    _lib.check(_lib.load().wc_critic_proj_bwd_f32(_ptr(y), _ptr(w_out), _ptr(emb), _ptr(cls), _ptr(g_out), N, H * W, C, emb.shape[0],
+                                                  int(bool(sum_pool)), _ptr(dy), _stream()), "wc_critic_proj_bwd_f32")
+    return dy
+
+
+def hip_projection_wgrad(feat, g_out, cls, K):
+    """wc_critic_proj_wgrad_f32 -> (dw_out (C,), db_out (1,), demb (K, C)); demb is written in full"""
+    N, C = feat.shape
+    dw_out = torch.empty(C, dtype=torch.float32, device=feat.device)
+    db_out = torch.empty(1, dtype=torch.float32, device=feat.device)
+    demb = torch.empty(K, C, dtype=torch.float32, device=feat.device)
+    _lib.check(_lib.load().wc_critic_proj_wgrad_f32(_ptr(feat), _ptr(g_out), _ptr(cls), N, C, K, _ptr(dw_out), _ptr(db_out), _ptr(demb),
+                                                    _stream()), "wc_critic_proj_wgrad_f32")
+    return dw_out, db_out, demb
+
+
+class _ProjectionTail(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, w_out, b_out, emb, cls, sum_pool):
+        y = _dense(y.detach())
+        w_out_c = _dense(w_out.detach().reshape(-1))
+        emb_c = _dense(emb.detach())
+        b_out_c = None if b_out is None else b_out.detach().contiguous()
+        idx = cls.detach().reshape(-1).to(torch.int32).contiguous()
+        feat, out = hip_projection_forward(y, w_out_c, b_out_c, emb_c, idx, sum_pool)
+        ctx.save_for_backward(y, w_out_c, emb_c, feat, idx)
+        ctx.meta = (bool(sum_pool), tuple(w_out.shape), b_out is not None)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        y, w_out, emb, feat, idx = ctx.saved_tensors
+        sum_pool, w_out_shape, has_b_out = ctx.meta
+        g_out = g_out.reshape(y.shape[0]).to(torch.float32).contiguous()
+        dy = hip_projection_backward(y, w_out, emb, idx, g_out, sum_pool) if ctx.needs_input_grad[0] else None
+        dw_out = db_out = demb = None
+        if any(ctx.needs_input_grad[1:4]):
+            dw_out, db_out, demb = hip_projection_wgrad(feat, g_out, idx, emb.shape[0])
+            dw_out = dw_out.view(w_out_shape)
+        return dy, dw_out, db_out if has_b_out else None, demb, None, None
+
+
+def projection_route(y, w_out, b_out, emb, cls):
+    """whether projection_tail runs these tensors on the kernels"""
+    if not (torch.is_tensor(y) and y.is_cuda and y.dtype == torch.float32 and y.dim() == 4):
+        return False
+    if not (all(_f32(t) for t in (w_out, b_out, emb)) and emb is not None and emb.dim() == 2 and cls.is_cuda and not cls.is_floating_point()):
+        return False
+    N, H, W, C = y.shape
+    if w_out.numel() != C or emb.shape[1] != C or cls.numel() != N:
+        return False
+    return bool(_lib.load().wc_critic_proj_supported(N, H * W, C, emb.shape[0]))
+
+
+def projection_tail(y, w_out, b_out, emb, cls, sum_pool=True):
+    """y (N, H, W, C) NHWC, the last block's output BEFORE its ReLU; w_out (1, C) or (C,) and emb (K, C) -- a layer's weight or the
+    spectral-norm op's output --, cls (N,) or (N, 1) integers.  -> out (N, 1) = f . (w_out + emb[cls]) + b_out; gradients go to y, w_out,
+    b_out and emb (dense, every row written)."""
+    global last_route
+    if projection_route(y, w_out, b_out, emb, cls):
+        last_route = 'hip'
+        return _ProjectionTail.apply(y, w_out, b_out, emb, cls, bool(sum_pool))
+    last_route = 'torch'
+    return torch_projection_tail(y, w_out, b_out, emb, cls, sum_pool)

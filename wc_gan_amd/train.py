@@ -544,6 +544,35 @@ ACGAN_SCHEDULES = {
 }
 
 
+FUSED_PROJECTION_SHIPS = True       # profiles/projection_step.json: faster than torch's tail in every round at all three shapes
+
+
+def _sn_cond(classes, after_norm, filters_emb=None):
+    """scripts/cifar10_resnet_sn_cond_sa.sh (ufconv, --filters_emb 4), scripts/cifar100_resnet_sn_cond.sh (ucconv) and
+    scripts/cifar100_resnet_sn_cond_sa.sh (ufconv, --filters_emb 10): CIFAR10_COND's networks -- hinge objectives, --gan_type PROJECTIVE,
+    generator_filters 128, discriminator_filters 256, norms d / uconv at the last site, SN critic, --sum_pool 1 -- with the script's class
+    count and block after-norm.  With 100 classes and 64 samples the generator's block sites run per-sample colouring tables.
+    fused_projection: the critic's tail on tail.projection_tail, as profiles/projection_step.json decided."""
+    emb = {} if filters_emb is None else dict(filters_emb=filters_emb)
+    return dict(
+        generator=dict(block_sizes=(128, 128, 128), resamples=("UP", "UP", "UP"), first_block_shape=(4, 4, 128), number_of_classes=classes,
+                       block_norm='d', block_after_norm=after_norm, last_norm='d', last_after_norm='uconv', gan_type='PROJECTIVE', **emb),
+        discriminator=dict(input_image_shape=(32, 32, 3), block_sizes=(256, 256, 256, 256), resamples=('DOWN', 'DOWN', 'SAME', 'SAME'),
+                           number_of_classes=classes, type='PROJECTIVE', spectral=True, sum_pool=True, conv_singular=False,
+                           fused_projection=FUSED_PROJECTION_SHIPS, **emb),
+        image_shape=(32, 32, 3), conditional=True)
+
+
+# the three further conditional SN recipes; NOT in CONFIGS (bench.py's names), their schedules in a table of their own
+PROJECTION_CONFIGS = {'cifar10_cond_sa': _sn_cond(10, 'ufconv', filters_emb=4), 'cifar100_cond': _sn_cond(100, 'ucconv'),
+                      'cifar100_cond_sa': _sn_cond(100, 'ufconv', filters_emb=10)}
+PROJECTION_SCHEDULES = {
+    'cifar10_cond_sa': dict(lr_decay_schedule='linear', number_of_epochs=50),           # scripts/cifar10_resnet_sn_cond_sa.sh:8
+    'cifar100_cond': dict(lr_decay_schedule='linear', number_of_epochs=50),             # scripts/cifar100_resnet_sn_cond.sh:8
+    'cifar100_cond_sa': dict(lr_decay_schedule='linear', number_of_epochs=50),          # scripts/cifar100_resnet_sn_cond_sa.sh:8
+}
+
+
 # --lr_decay_schedule / --number_of_epochs of each recipe's script: GanTrainer's arguments of the same names (the config tables above carry
 # the networks alone and are left as they are).  build_trainer(CONFIGS[name], **RECIPE_SCHEDULES[name]) trains the recipe at its script's rates.
 RECIPE_SCHEDULES = {
@@ -589,6 +618,15 @@ def zca_config(config):
     import copy
     out = copy.deepcopy(config)
     out['generator'].update(decomposition='zca')
+    return out
+
+
+def fused_projection_config(config):
+    """The same recipe with the projection critic's tail on the HIP route (make_discriminator(fused_projection=True), DESIGN.md section
+    4.20): a copy of any entry, the entry itself is left alone.  Without effect on a critic of another type."""
+    import copy
+    out = copy.deepcopy(config)
+    out['discriminator'].update(fused_projection=True)
     return out
 
 
