@@ -749,6 +749,49 @@ int    wc_conv_bwd_pair_f16x3(const void* ghi, const void* glo, const float* gsc
                               int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
                               const float* colsum_partials, float* db, void* ws_dw, size_t ws_dw_bytes, wc_stream_t stream);
 
+/* A k-split finish that goes on to do what the next launch did (the critic's 128-channel blocks at 8x8).  Where a convolution's tap loop is
+ * shared over workgroups (wc_conv_tail_supported: the geometries of wc_conv_res_supported), an elementwise launch finishes it -- and the
+ * very next launch used to read that fp32 tensor back only to re-express it.  These entries run the convolution of wc_conv_f16x3 (no ReLU) /
+ * the layer backward of wc_conv_bwd_pair_f16x3 unchanged and give the finish a tail, wc_conv_tail.kind:
+ *   WC_CONV_TAIL_SPLIT   y = (conv + bias) + res (res nullable: wc_conv_res_f16x3's value) in fp32 AND the planes of relu(y), scaled by the
+ *                        record `hist` of the convolution that reads them: hi / lo / scale / hist as wc_conv_split_hist_f32 with relu = 1
+ *                        leaves them, the record's pairs and carried maximum included.  The forward entry only.
+ *   WC_CONV_TAIL_MASKED  y (the data gradient) in fp32 AND the planes of y * (mask > 0), mask of y's shape: hi / lo / scale / hist and the
+ *                        kAmaxBlocks = 512 partial rows colsum_partials (nullable; C = Cout) as wc_conv_split_hist_masked_f32 with slope 0
+ *                        leaves them.
+ *   WC_CONV_TAIL_DX      out = (mask > 0 ? conv : 0) + other, mask and other of the output's shape: wc_conv_block_dx_f32 with down = 0 on
+ *                        the finished value, which is never written (y / dx may be NULL).  out must not alias an input.
+ * redo != 0 (SPLIT, MASKED): the gated second pass of the history-scaled split follows, as behind the split entries.  The record must be
+ * SEEDED (the site's first call goes through the split entries with bootstrap bit 0); every value has the bits of the two launches it
+ * replaces -- the finish launch runs the split's 512 x 256 grid.  Geometries without a shared tap loop: WC_ERR_SHAPE, the caller keeps the
+ * two launches.  Additive: WC_CORE_API keeps its list and WC_ABI_VERSION its value. */
+#define WC_CONV_TAIL_SPLIT 1
+#define WC_CONV_TAIL_MASKED 2
+#define WC_CONV_TAIL_DX 3
+typedef struct wc_conv_tail {
+    int kind;
+    int redo;
+    const float* res;                 /* SPLIT */
+    const float* mask;                /* MASKED, DX */
+    const float* other;               /* DX */
+    float* out;                       /* DX */
+    void* hi; void* lo; float* scale; float* hist;      /* SPLIT, MASKED */
+    float* colsum_partials; int C;    /* MASKED */
+} wc_conv_tail;
+int wc_conv_tail_supported(const wc_conv_geom* g);
+int wc_conv_tail_f16x3(const void* xhi, const void* xlo, const float* xscale, const void* wimage, const float* wscale,
+                       const float* bias, const void* zero_line, const wc_conv_geom* g, float* y,
+                       void* ws, size_t ws_bytes, const wc_conv_tail* tail, wc_stream_t stream);
+int wc_conv_bwd_pair_tail_f16x3(const void* ghi, const void* glo, const float* gscale, const void* wimage, const float* wscale,
+                                const void* zero_line, const wc_conv_geom* gd, float* dx, void* ws_dx, size_t ws_dx_bytes,
+                                const void* xhi, const void* xlo, const float* xscale, const wc_conv_geom* gf, float* dw,
+                                int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
+                                const float* colsum_partials, float* db, void* ws_dw, size_t ws_dw_bytes,
+                                const wc_conv_tail* tail, wc_stream_t stream);
+/* the gated second pass of wc_conv_split_hist_masked_f32 alone (behind a MASKED tail; arguments as there) */
+int wc_conv_split_redo_masked_f32(const float* t, const float* a, int64_t n, float slope, void* hi, void* lo, float* scale, float* hist,
+                                  wc_stream_t stream);
+
 /* Bandwidth yardstick used by bench.py: dst[i] = src[i] (float4 grid-stride copy), same stream rules. */
 int wc_stream_copy_f32(const float* src, float* dst, int64_t n, wc_stream_t stream);
 

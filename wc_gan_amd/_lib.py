@@ -168,6 +168,13 @@ SIGNATURES = {
     "wc_conv_bwd_pair_f16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wc_conv_tail_supported": (c_int, [c_void_p]),
+    "wc_conv_tail_f16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_size_t, c_void_p, c_void_p]),
+    "wc_conv_bwd_pair_tail_f16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                            c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "wc_conv_split_redo_masked_f32": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wc_std_stats_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "wc_std_stats_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "wc_std_factor_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_double, c_double, c_int, c_int, c_void_p, c_void_p,
@@ -255,6 +262,14 @@ class ConvWeightsJob(ctypes.Structure):  # wc_conv_weights_job
     _fields_ = [("w", c_void_p), ("stride_k", c_int64), ("stride_n", c_int64), ("stride_r", c_int64), ("stride_s", c_int64),
                 ("n_elems", c_int64), ("g", c_void_p), ("image", c_void_p), ("scale", c_void_p), ("amax", c_void_p),
                 ("amax_count", c_int), ("pair_of", c_int)]
+
+
+TAIL_SPLIT, TAIL_MASKED, TAIL_DX = 1, 2, 3      # WC_CONV_TAIL_*
+
+
+class ConvTail(ctypes.Structure):        # wc_conv_tail
+    _fields_ = [("kind", c_int), ("redo", c_int), ("res", c_void_p), ("mask", c_void_p), ("other", c_void_p), ("out", c_void_p),
+                ("hi", c_void_p), ("lo", c_void_p), ("scale", c_void_p), ("hist", c_void_p), ("colsum_partials", c_void_p), ("C", c_int)]
 
 
 class ConvAbsmaxJob(ctypes.Structure):   # wc_conv_absmax_job

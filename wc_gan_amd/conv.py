@@ -111,7 +111,7 @@ def supported(x, w, kind):
 class _Plan:
     """Everything about a call that depends on the shapes only, built once: the two geometries, the weight axes, the
     support verdict and the workspace sizes (the per-call host work is what is left: a few allocations and launches)."""
-    __slots__ = ('ok', 'fwd', 'bwd', 'fwd_ws', 'bwd_ws', 'wrw_ws', 'fwd_ptr', 'bwd_ptr', 'pair', 'res')
+    __slots__ = ('ok', 'fwd', 'bwd', 'fwd_ws', 'bwd_ws', 'wrw_ws', 'fwd_ptr', 'bwd_ptr', 'pair', 'res', 'tail', 'bwd_tail')
 
     def __init__(self, kind, N, H, W, wshape):
         class _W:                                   # shape-only stand-in for the weight
@@ -128,6 +128,9 @@ class _Plan:
         self.pair = self.ok and bool(lib.wc_conv_bwd_pair_supported(self.bwd_ptr, self.fwd_ptr))
         # a residual operand in the forward's finish (wc_conv_res_f16x3): the layers whose tap loop is shared over workgroups
         self.res = self.ok and bool(lib.wc_conv_res_supported(self.fwd_ptr))
+        # a finish launch that can go on to its follower's work (wc_conv_tail_f16x3): the forward's, the data gradient's
+        self.tail = self.ok and bool(lib.wc_conv_tail_supported(self.fwd_ptr))
+        self.bwd_tail = self.ok and bool(lib.wc_conv_tail_supported(self.bwd_ptr))
 
 
 _plans = {}
@@ -574,16 +577,81 @@ def weight_gradient(x_planes, g_planes, geom, w, k_axis, n_axis, nbytes=None, co
     return dw
 
 
-def backward_pair(g_planes, image, x_planes, plan, w, colsum=None):
+def _reader_record(site, role, device):
+    """The record of `site` for `role` when a convolution's finish may write that reader's planes itself (a *_TAIL entry): the history
+    route on, the site in training mode, the record there and seeded -- else None, and the caller keeps the finish and the split as two
+    launches (the first call of a site, eval mode, a capture that meets a site without a record).  Never creates a record."""
+    if not (SPLIT_HIST and site is not None and getattr(site, 'training', True)):
+        return None
+    h = site.__dict__.get('_wc_split_hist', {}).get(role)
+    if h is None or not h[1] or h[0].device != device:
+        return None
+    return h
+
+
+class _Tail:
+    """The operands of a finish's tail (include/wc_hip.h wc_conv_tail) with the tensors it writes: `planes` = (hi, lo, scale[, partial rows])
+    of SPLIT / MASKED, `out` of DX.  Holds every tensor the struct points at for as long as it lives."""
+
+    def __init__(self, kind, shape, device, record=None, role='x', res=None, mask=None, other=None, colsum=False):
+        t = self.c = _lib.ConvTail()
+        t.kind = kind
+        self.keep = (res, mask, other, record)
+        self.planes = self.out = None
+        if kind == _lib.TAIL_DX:
+            self.out = torch.empty(shape, dtype=torch.float32, device=device)
+            t.mask, t.other, t.out = _ptr(mask), _ptr(other), _ptr(self.out)
+            return
+        both = torch.empty((2,) + tuple(shape), dtype=torch.float16, device=device)
+        scale = torch.empty(1 + 512, dtype=torch.float32, device=device)      # (split_planes' layout: [scale | scratch])
+        t.hi, t.lo, t.scale, t.hist = _ptr(both[0]), _ptr(both[1]), _ptr(scale), _ptr(record[0])
+        t.redo = 1 if _guarded(role) else 0
+        self.planes = (both[0], both[1], scale)
+        if kind == _lib.TAIL_SPLIT:
+            t.res = _ptr(res) if res is not None else None
+            return
+        t.mask = _ptr(mask)
+        if colsum:
+            part = torch.empty((512, shape[-1]), dtype=torch.float32, device=device)
+            t.colsum_partials, t.C = _ptr(part), shape[-1]
+            self.planes += (part,)
+
+
+def _dense32(t, shape):
+    return t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.dtype == torch.float32
+
+
+def run_tail(planes, image, geom, tail, bias=None, nbytes=None):
+    """run(planes, image, geom, bias) on a geometry _Plan.tail / .bwd_tail takes, its finish going on to `tail`'s work
+    (wc_conv_tail_f16x3): -> the fp32 output (None for a DX tail: the value is never written); tail.planes / tail.out hold the rest."""
+    hi, lo, xs = planes
+    img, ws = image
+    lib = _lib.load()
+    y = None
+    if tail.c.kind != _lib.TAIL_DX:
+        y = torch.empty((geom.N, geom.Hout, geom.Wout, geom.Cout), dtype=torch.float32, device=hi.device)
+    if nbytes is None:
+        nbytes = lib.wc_conv_workspace_bytes(ctypes.addressof(geom))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=hi.device) if nbytes else None
+    _lib.check(lib.wc_conv_tail_f16x3(_ptr(hi), _ptr(lo), _ptr(xs), _ptr(img), _ptr(ws), _ptr(bias) if bias is not None else None,
+                                      _ptr(_zero_line(hi.device)), ctypes.addressof(geom), _ptr(y), _ptr(work), nbytes,
+                                      ctypes.addressof(tail.c), _stream()), "wc_conv_tail_f16x3")
+    return y
+
+
+def backward_pair(g_planes, image, x_planes, plan, w, colsum=None, tail=None):
     """run(g_planes, image, plan.bwd) and weight_gradient(x_planes, g_planes, plan.fwd, w, ...) of one layer in two launches
-    (wc_conv_bwd_pair_f16x3; plan.pair says whether the library takes the layer): -> (dx, dW, db | None), the bits of the two calls."""
+    (wc_conv_bwd_pair_f16x3; plan.pair says whether the library takes the layer): -> (dx, dW, db | None), the bits of the two calls.
+    tail (plan.bwd_tail; a MASKED or DX _Tail): the data gradient's finish goes on to the tail's work (dx None behind a DX tail)."""
     lib = _lib.load()
     gh, gl, gs = g_planes[:3]
     xh, xl, xs = x_planes
     img, ws = image
     gf, kf, nf = plan.fwd
     gb = plan.bwd[0]
-    dx = torch.empty((gb.N, gb.Hout, gb.Wout, gb.Cout), dtype=torch.float32, device=gh.device)
+    dx = None
+    if tail is None or tail.c.kind != _lib.TAIL_DX:
+        dx = torch.empty((gb.N, gb.Hout, gb.Wout, gb.Cout), dtype=torch.float32, device=gh.device)
     dw = torch.empty_like(w)
     if dw.stride() != w.stride():
         raise ValueError("weight must be dense")
@@ -591,6 +659,13 @@ def backward_pair(g_planes, image, x_planes, plan, w, colsum=None):
     work_dw = torch.empty(plan.wrw_ws, dtype=torch.uint8, device=gh.device)
     db = torch.empty(gf.Cout, dtype=torch.float32, device=w.device) if colsum is not None else None
     zero = _zero_line(gh.device)
+    if tail is not None:
+        _lib.check(lib.wc_conv_bwd_pair_tail_f16x3(_ptr(gh), _ptr(gl), _ptr(gs), _ptr(img), _ptr(ws), _ptr(zero), plan.bwd_ptr, _ptr(dx),
+                                                   _ptr(work_dx), plan.bwd_ws,
+                                                   _ptr(xh), _ptr(xl), _ptr(xs), plan.fwd_ptr, _ptr(dw), w.stride(kf), w.stride(nf),
+                                                   w.stride(2), w.stride(3), _ptr(colsum), _ptr(db), _ptr(work_dw), plan.wrw_ws,
+                                                   ctypes.addressof(tail.c), _stream()), "wc_conv_bwd_pair_tail_f16x3")
+        return dx, dw, db
     _lib.check(lib.wc_conv_bwd_pair_f16x3(_ptr(gh), _ptr(gl), _ptr(gs), _ptr(img), _ptr(ws), _ptr(zero), plan.bwd_ptr, _ptr(dx),
                                           _ptr(work_dx), plan.bwd_ws,
                                           _ptr(xh), _ptr(xl), _ptr(xs), plan.fwd_ptr, _ptr(dw), w.stride(kf), w.stride(nf), w.stride(2),
@@ -963,17 +1038,20 @@ def _images(w, plan, both, site=None):
     return weight_image(w, gf, kf, nf, site=site), None
 
 
-def _layer_gradients(g_planes, fused_db, x_planes, w, plan, bwd_image, need_dx, need_dw):
+def _layer_gradients(g_planes, fused_db, x_planes, w, plan, bwd_image, need_dx, need_dw, tail=None):
     """The launches of _FastConv.backward behind the split of the output gradient -> (dx, dW, db | None); dx is the convolution's data
-    gradient as it comes (no activation's backward)."""
+    gradient as it comes (no activation's backward).  tail (need_dx, plan.bwd_tail): the data gradient's finish does the tail's work too."""
     cs = g_planes[3] if fused_db else None
     if need_dx and need_dw and bwd_image is not None and plan.pair:
-        return backward_pair(g_planes, bwd_image, x_planes, plan, w, colsum=cs)
+        return backward_pair(g_planes, bwd_image, x_planes, plan, w, colsum=cs, tail=tail)
     dx = dw = db = None
     if need_dx:
         gb, kb, nb = plan.bwd
         image = bwd_image if bwd_image is not None else weight_image(w, gb, kb, nb)
-        dx = run(g_planes[:3], image, gb, nbytes=plan.bwd_ws)
+        if tail is not None:
+            dx = run_tail(g_planes[:3], image, gb, tail, nbytes=plan.bwd_ws)
+        else:
+            dx = run(g_planes[:3], image, gb, nbytes=plan.bwd_ws)
     if need_dw:
         gf, kf, nf = plan.fwd
         if fused_db:
@@ -987,39 +1065,70 @@ def _pool2(x):
     return F.avg_pool2d(x.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1).contiguous()
 
 
+# The k-split finishes of the block write what their next launch read back (csrc/wc_conv.hip conv_finish_tail_kernel; DESIGN.md section
+# 4.5): F1 conv1's finish -> conv2's input planes, F2 conv2's finish (with the residual) -> the NEXT block's conv1 input planes, B1 conv2's
+# data-gradient finish -> conv1's masked output-gradient planes (and the bias gradient's partial rows), B2 conv1's data-gradient finish ->
+# the SAME block's input gradient; B1 and B2 where the caller asks for them (critic_block's backward_tails: the critic's pass).  Each where the plan says the convolution shares its tap loop (_Plan.tail / .bwd_tail) and the
+# reader's record can be used (_reader_record); otherwise the two launches run as before.  Same bits either way.  FUSED_FINISH = False:
+# the two-launch route everywhere; the four flags below switch one part each (tests, tools/finish_split_bench.py).
+FUSED_FINISH = True
+FUSED_FINISH_F1 = True
+FUSED_FINISH_F2 = True
+FUSED_FINISH_B1 = True
+FUSED_FINISH_B2 = True
+
+
 class _CriticBlock(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, ws, bs, sites, plans, down):
+    def forward(ctx, x, w1, b1, w2, b2, ws, bs, sites, plans, down, next_site=None, xh=None, xl=None, xs=None, backward_tails=False):
         conv1, conv2, shortcut = sites
         p1, p2, ps = plans
         need = ctx.needs_input_grad
         need_h = need[0] or need[1] or need[2]
-        x_pl = split_planes(x, relu=True, site=conv1, role='x')
+        # xh, xl, xs: the planes of relu(x) for conv1, written by the block in front (its conv2's finish, F2) -- this block's first split
+        x_pl = (xh, xl, xs) if xh is not None else split_planes(x, relu=True, site=conv1, role='x')
         img1, bimg1 = _images(w1, p1, need[0], conv1)
-        h = run(x_pl, img1, p1.fwd[0], b1, nbytes=p1.fwd_ws)
-        h_pl = split_planes(h, relu=True, site=conv2, role='x')
+        rec = _reader_record(conv2, 'x', x.device) if (FUSED_FINISH and FUSED_FINISH_F1 and p1.tail) else None
+        if rec is not None:
+            t1 = _Tail(_lib.TAIL_SPLIT, (p1.fwd[0].N, p1.fwd[0].Hout, p1.fwd[0].Wout, p1.fwd[0].Cout), x.device, record=rec, role='x')
+            h = run_tail(x_pl, img1, p1.fwd[0], t1, bias=b1, nbytes=p1.fwd_ws)
+            h_pl = t1.planes
+        else:
+            h = run(x_pl, img1, p1.fwd[0], b1, nbytes=p1.fwd_ws)
+            h_pl = split_planes(h, relu=True, site=conv2, role='x')
         img2, bimg2 = _images(w2, p2, need_h, conv2)
         s, s_pl, bimgs = x, (), None
         if ws is not None:
             s_pl = split_planes(_pool2(x) if down else x, site=shortcut, role='x')
             imgs, bimgs = _images(ws, ps, need[0], shortcut)
             s = run(s_pl, imgs, ps.fwd[0], bs, nbytes=ps.fwd_ws)
-        if p2.res and FUSED_RESIDUAL:
-            y = run(h_pl, img2, p2.fwd[0], b2, nbytes=p2.fwd_ws, res=s)
+        n_pl = ()
+        g2 = p2.fwd[0]
+        rec = None
+        if next_site is not None and FUSED_FINISH and FUSED_FINISH_F2 and FUSED_RESIDUAL and p2.tail and _dense32(s, (g2.N, g2.Hout, g2.Wout, g2.Cout)):
+            rec = _reader_record(next_site, 'x', x.device)
+        if rec is not None:
+            t2 = _Tail(_lib.TAIL_SPLIT, (g2.N, g2.Hout, g2.Wout, g2.Cout), x.device, record=rec, role='x', res=s)
+            y = run_tail(h_pl, img2, g2, t2, bias=b2, nbytes=p2.fwd_ws)
+            n_pl = t2.planes
+        elif p2.res and FUSED_RESIDUAL:
+            y = run(h_pl, img2, g2, b2, nbytes=p2.fwd_ws, res=s)
         else:
-            y = run(h_pl, img2, p2.fwd[0], b2, nbytes=p2.fwd_ws) + s
+            y = run(h_pl, img2, g2, b2, nbytes=p2.fwd_ws) + s
         ctx.save_for_backward(x, h, w1, w2, *x_pl, *h_pl, *s_pl, *((ws,) if ws is not None else ()))
         ctx.sites, ctx.plans, ctx.down = sites, plans, down
+        ctx.backward_tails = bool(backward_tails)
         ctx.images = (bimg1, bimg2, bimgs)
         ctx.has_bias = (b1 is not None, b2 is not None, bs is not None)
         # h leaves only for whoever watches the block's second norm site: no gradient, and none made up for it in backward
-        # (autograd would otherwise hand backward a zero-filled tensor of h's shape: a pass over memory per block)
-        ctx.mark_non_differentiable(h)
+        # (autograd would otherwise hand backward a zero-filled tensor of h's shape: a pass over memory per block); the planes for the
+        # next block likewise
+        ctx.mark_non_differentiable(h, *n_pl)
         ctx.set_materialize_grads(False)
-        return y, h
+        return (y, h) + tuple(n_pl)
 
     @staticmethod
-    def backward(ctx, g, _gh):
+    def backward(ctx, g, _gh, *_gp):
         saved = ctx.saved_tensors
         x, h, w1, w2 = saved[:4]
         x_pl, h_pl = saved[4:7], saved[7:10]
@@ -1029,7 +1138,7 @@ class _CriticBlock(torch.autograd.Function):
         need = ctx.needs_input_grad
         need_h = need[0] or need[1] or need[2]
         if g is None:               # (gradients are not materialised: nothing reached y)
-            return (None,) * 10
+            return (None,) * 15
         g = g.contiguous()
         dx = dw1 = db1 = dw2 = db2 = dws = dbs = dx1 = None
 
@@ -1039,19 +1148,15 @@ class _CriticBlock(torch.autograd.Function):
         # conv2: its output gradient is the block's; its data gradient stays unmasked
         fused2 = bias_rides(ctx.has_bias[1], need[4], need[3], g.shape[-1])
         g2 = split_planes(g, colsum=fused2, site=conv2, role='g')
-        dh, dw2, db2 = _layer_gradients(g2, fused2, h_pl, w2, p2, bimg2, need_h, need[3])
+        fused1 = need_h and bias_rides(ctx.has_bias[0], need[2], need[1], h.shape[-1])
+        # B1: conv2's data-gradient finish writes conv1's masked output-gradient planes
+        rec = None
+        if need_h and ctx.backward_tails and FUSED_FINISH and FUSED_FINISH_B1 and FUSED_MASKED_SPLIT and p2.bwd_tail:
+            rec = _reader_record(conv1, 'g', g.device)
+        tb1 = _Tail(_lib.TAIL_MASKED, tuple(h.shape), g.device, record=rec, role='g', mask=h, colsum=fused1) if rec is not None else None
+        dh, dw2, db2 = _layer_gradients(g2, fused2, h_pl, w2, p2, bimg2, need_h, need[3], tail=tb1)
         if ctx.has_bias[1] and need[4] and not fused2:
             db2 = g.sum((0, 1, 2))
-        # conv1: the ReLU between the two (mask: conv1's output h) happens while conv2's data gradient is split
-        if need_h:
-            fused1 = bias_rides(ctx.has_bias[0], need[2], need[1], h.shape[-1])
-            if FUSED_MASKED_SPLIT:
-                g1 = split_planes_masked(dh, h, site=conv1, role='g', colsum=fused1)
-            else:
-                g1 = split_planes(torch.ops.aten.threshold_backward(dh, h, 0), colsum=fused1, site=conv1, role='g')
-            dx1, dw1, db1 = _layer_gradients(g1, fused1, x_pl, w1, p1, bimg1, need[0], need[1])
-            if ctx.has_bias[0] and need[2] and not fused1:
-                db1 = torch.ops.aten.threshold_backward(dh, h, 0).sum((0, 1, 2))
         # the shortcut, as its own node ran it
         other = g
         if ps is not None:
@@ -1061,7 +1166,25 @@ class _CriticBlock(torch.autograd.Function):
             other, dws, dbs = _layer_gradients(gs, fuseds, saved[10:13], ws, ps, bimgs, need[0], need[5])
             if ctx.has_bias[2] and need[6] and not fuseds:
                 dbs = g.sum((0, 1, 2))
-        if need[0]:
+        # conv1: the ReLU between the two (mask: conv1's output h) happens while conv2's data gradient is split
+        if need_h:
+            if tb1 is not None:
+                g1 = tb1.planes
+            elif FUSED_MASKED_SPLIT:
+                g1 = split_planes_masked(dh, h, site=conv1, role='g', colsum=fused1)
+            else:
+                g1 = split_planes(torch.ops.aten.threshold_backward(dh, h, 0), colsum=fused1, site=conv1, role='g')
+            # B2: conv1's data-gradient finish writes the block input's gradient (identity-resolution blocks: `other` has x's shape)
+            tb2 = None
+            if (need[0] and ctx.backward_tails and FUSED_FINISH and FUSED_FINISH_B2 and FUSED_BLOCK_DX and not ctx.down and p1.bwd_tail
+                    and _dense32(other, x.shape)):
+                tb2 = _Tail(_lib.TAIL_DX, tuple(x.shape), g.device, mask=x, other=other)
+            dx1, dw1, db1 = _layer_gradients(g1, fused1, x_pl, w1, p1, bimg1, need[0], need[1], tail=tb2)
+            if tb2 is not None:
+                dx = tb2.out
+            if ctx.has_bias[0] and need[2] and not fused1:
+                db1 = torch.ops.aten.threshold_backward(dh, h, 0).sum((0, 1, 2))
+        if need[0] and dx is None:
             if FUSED_BLOCK_DX:
                 dx = block_input_gradient(dx1, x, other, ctx.down)
             else:
@@ -1070,11 +1193,18 @@ class _CriticBlock(torch.autograd.Function):
                     other = torch.ops.aten.avg_pool2d_backward(other.permute(0, 3, 1, 2), x.permute(0, 3, 1, 2), [2, 2], [2, 2], [0, 0],
                                                                False, True, None).permute(0, 2, 3, 1)
                 dx = dx + other
-        return dx, dw1, db1, dw2, db2, dws, dbs, None, None, None
+        return dx, dw1, db1, dw2, db2, dws, dbs, None, None, None, None, None, None, None, None
 
 
-def critic_block(x, w1, b1, w2, b2, ws, bs, sites, plans, down):
+def critic_block(x, w1, b1, w2, b2, ws, bs, sites, plans, down, next_site=None, x_planes=None, backward_tails=False):
     """One critic block behind the first (see above): x NHWC fp32 on the GPU, the three weights as their layers hand them out (ws / bs
     None: identity shortcut), sites = the three layer objects (the shortcut's None with ws), plans from critic_block_plans.
-    -> (y, h): the block's output and, detached, conv1's output (the tensor the block's second norm site sees)."""
-    return _CriticBlock.apply(x, w1, b1, w2, b2, ws, bs, sites, plans, down)
+    next_site: the layer that reads relu(y) next (the following block's conv1) -- its input planes then come out of conv2's finish where
+    that can write them.  x_planes: such planes of relu(x), from the block in front: this block's first split is skipped.
+    backward_tails: the finishes of the block's two data gradients do their followers' work as well (B1, B2 above).  The critic's pass
+    asks for it (Discriminator.forward); a block called on its own keeps its backward's launches -- the masked split and the block
+    input's gradient as launches of their own, which tests/test_critic_glue_gpu.py names for a block called that way.
+    -> (y, h, planes): the block's output, detached conv1's output (the tensor the block's second norm site sees), and the (hi, lo,
+    scale) planes of relu(y) for next_site or None."""
+    out = _CriticBlock.apply(x, w1, b1, w2, b2, ws, bs, sites, plans, down, next_site, *(x_planes if x_planes is not None else (None, None, None)), backward_tails)
+    return out[0], out[1], (tuple(out[2:5]) if len(out) > 2 else None)

@@ -27,9 +27,12 @@
 //   * one layer's backward where both gradients run on 128 x 128 tiles (the critic's 128-channel layers): the data gradient's and the
 //     weight gradient's workgroups in ONE grid (conv_bwd_pair_kernel) and one launch that finishes both (conv_pair_reduce_kernel) --
 //     the kernels' bodies are __device__ functions of the block coordinates, shared with the launches of their own; same bits.
+//   * where a k-split's finish was followed by a launch that read its result back only to re-express it (the critic at 8x8), the finish does
+//     that work too: the reader's planes, or the block input's gradient (conv_finish_tail_kernel, conv_pair_reduce_tail_kernel); same bits.
 //   * conv(relu(x)) and conv(leaky_relu(x)) apply the activation while x is split (conv_split_*_kernel, split_act).
 // MFMA-bound by design: 3 * 2*M*Cout*K flop on the fp16 pipe against 2*M*Cout*K on the fp32 pipe (157 TFLOP/s peak).
 #include "wc_common.h"
+#include "wc_mask.h"
 #include "../../include/wc_hip.h"
 #include <stdlib.h>
 #include <string.h>
@@ -253,6 +256,33 @@ struct KsplitReduceArgs {
     const float* xscale; const float* wscale; const float* bias; int relu; float* y;
 };
 
+// the finished value of float4 i: (sum of the shares in order) * inv + bias (, ReLU) (+ res).  ONE source for every kernel that finishes a
+// k-split -- the plain finish below and the finishes that go on to write what the next launch used to read back (conv_finish_split_body,
+// conv_finish_dx_body): whether `v * inv` and `+ bias` contract is decided here, for all of them
+__device__ __forceinline__ f32x4 conv_ksplit_finish_elem(const float* __restrict__ partial, int ksplit, int64_t n4, int cout, const float inv,
+                                                         const float* __restrict__ bias, int relu, const float* __restrict__ res, const int64_t i)
+{
+    f32x4 v = *reinterpret_cast<const f32x4*>(partial + 4 * i);
+    int z = 1;
+    for (; z + 3 < ksplit; z += 4) {                 // four shares in flight, added in order
+        f32x4 t[4];
+        #pragma unroll
+        for (int u = 0; u < 4; ++u) t[u] = *reinterpret_cast<const f32x4*>(partial + 4 * ((z + u) * n4 + i));
+        #pragma unroll
+        for (int u = 0; u < 4; ++u) v += t[u];
+    }
+    for (; z < ksplit; ++z) v += *reinterpret_cast<const f32x4*>(partial + 4 * (z * n4 + i));
+    v = v * inv;
+    if (bias) v += *reinterpret_cast<const f32x4*>(bias + (4 * i) % cout);
+    if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+    if (res) {
+        const f32x4 r = *reinterpret_cast<const f32x4*>(res + 4 * i);
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = __fadd_rn(v[j], r[j]);        // (its own rounding: never contracted into the line above)
+    }
+    return v;
+}
+
 __device__ __forceinline__ void conv_ksplit_reduce_body(const float* __restrict__ partial, int ksplit, int64_t n4, int cout,
                                                         const float* __restrict__ xscale, const float* __restrict__ wscale,
                                                         const float* __restrict__ bias, int relu, float* __restrict__ y,
@@ -261,27 +291,8 @@ __device__ __forceinline__ void conv_ksplit_reduce_body(const float* __restrict_
     // res (y's shape, nullable): the residual block's other branch, added to the finished value -- y = (acc * inv + bias) + res, the bits of
     // the elementwise add that used to read y straight back (discriminator.py:41-54 `Add()([h, s])`)
     const float inv = 1.0f / (xscale[0] * wscale[0]);
-    for (int64_t i = (int64_t)bid * 256 + threadIdx.x; i < n4; i += (int64_t)nblocks * 256) {
-        f32x4 v = *reinterpret_cast<const f32x4*>(partial + 4 * i);
-        int z = 1;
-        for (; z + 3 < ksplit; z += 4) {                 // four shares in flight, added in order
-            f32x4 t[4];
-            #pragma unroll
-            for (int u = 0; u < 4; ++u) t[u] = *reinterpret_cast<const f32x4*>(partial + 4 * ((z + u) * n4 + i));
-            #pragma unroll
-            for (int u = 0; u < 4; ++u) v += t[u];
-        }
-        for (; z < ksplit; ++z) v += *reinterpret_cast<const f32x4*>(partial + 4 * (z * n4 + i));
-        v = v * inv;
-        if (bias) v += *reinterpret_cast<const f32x4*>(bias + (4 * i) % cout);
-        if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-        if (res) {
-            const f32x4 r = *reinterpret_cast<const f32x4*>(res + 4 * i);
-            #pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = __fadd_rn(v[j], r[j]);        // (its own rounding: never contracted into the line above)
-        }
-        *reinterpret_cast<f32x4*>(y + 4 * i) = v;
-    }
+    for (int64_t i = (int64_t)bid * 256 + threadIdx.x; i < n4; i += (int64_t)nblocks * 256)
+        *reinterpret_cast<f32x4*>(y + 4 * i) = conv_ksplit_finish_elem(partial, ksplit, n4, cout, inv, bias, relu, res, i);
 }
 
 __global__ __launch_bounds__(256) void conv_ksplit_reduce_kernel(const float* __restrict__ partial, int ksplit, int64_t n4, int cout,
@@ -378,6 +389,20 @@ __global__ __launch_bounds__(256) void conv_leaky_bwd_kernel(float* __restrict__
 //     DOWN == true:   out = (x > 0 ? dx1 : 0) + 0.25 * ds[n][y / 2][x / 2][c]   ds = the shortcut's data gradient at half resolution
 // i.e. threshold_backward, the 2x2 average pooling's backward and the add that joins them, with their bits: the masked-out value is +0,
 // a NaN in x lets the gradient through (x <= 0 is false), 0.25 * ds is rounded on its own and the sum once.  c4 = C / 4, W, H of dx1.
+// (one source for the expression: conv_finish_dx_body applies it to a data gradient it has just finished)
+template <bool DOWN>
+__device__ __forceinline__ f32x4 conv_block_dx_elem(const f32x4 d, const f32x4 a, const f32x4 o)
+{
+    f32x4 r;
+    #pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float m = a[k] <= 0.f ? 0.f : d[k];
+        // (the pooling's backward accumulates its one term onto +0: a -0 quarter leaves it as +0)
+        r[k] = __fadd_rn(m, DOWN ? __fadd_rn(0.f, __fmul_rn(0.25f, o[k])) : o[k]);
+    }
+    return r;
+}
+
 template <bool DOWN>
 __global__ __launch_bounds__(256) void conv_block_dx_kernel(const float* __restrict__ dx1, const float* __restrict__ x,
                                                             const float* __restrict__ other, int64_t n4, int c4, int W, int H,
@@ -397,14 +422,7 @@ __global__ __launch_bounds__(256) void conv_block_dx_kernel(const float* __restr
             j = ((n * (H >> 1) + (yy >> 1)) * (W >> 1) + (xx >> 1)) * c4 + c;
         }
         const f32x4 o = *reinterpret_cast<const f32x4*>(other + 4 * j);
-        f32x4 r;
-        #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float m = a[k] <= 0.f ? 0.f : d[k];
-            // (the pooling's backward accumulates its one term onto +0: a -0 quarter leaves it as +0)
-            r[k] = __fadd_rn(m, DOWN ? __fadd_rn(0.f, __fmul_rn(0.25f, o[k])) : o[k]);
-        }
-        *reinterpret_cast<f32x4*>(out + 4 * i) = r;
+        *reinterpret_cast<f32x4*>(out + 4 * i) = conv_block_dx_elem<DOWN>(d, a, o);
     }
 }
 
@@ -481,14 +499,14 @@ __global__ __launch_bounds__(kAmaxBlocks) void conv_hist_seed_kernel(float* __re
     }
 }
 
-__global__ __launch_bounds__(256) void conv_split_hist_kernel(const float* __restrict__ x, int64_t n4, int relu, _Float16* __restrict__ hi,
-                                                              _Float16* __restrict__ lo, float* __restrict__ scale_out,
-                                                              float* __restrict__ hist, float* __restrict__ colsum, int c4n,
-                                                              float slope = 0.f)
+// The record's protocol and the split's per-element work as __device__ pieces: conv_split_hist_kernel and the k-split finishes that write
+// their reader's planes (conv_finish_split_body) are put together from the same ones, so a launch of either kind leaves the planes, the
+// scale word, the pairs and the carried maximum that the other would have left.
+struct HistPick { int src, tag; float s; };
+
+// pick: the complete array with the larger tag -> the scale of this call; workgroup 0 leaves the scale and the maximum it assumed
+__device__ __forceinline__ HistPick conv_hist_pick(float* __restrict__ hist, float* __restrict__ scale_out, const unsigned bid)
 {
-    __shared__ float red[4];
-    __shared__ f32x4 red4[256];
-    typedef float f32x2h __attribute__((ext_vector_type(2)));
     // every wave folds both arrays: the maximum and the smallest / largest tag of each (tags as int: __shfl_xor has no unsigned form --
     // an unsigned argument travels as a float and comes back rounded)
     typedef int i32x2h __attribute__((ext_vector_type(2)));
@@ -521,36 +539,130 @@ __global__ __launch_bounds__(256) void conv_split_hist_kernel(const float* __res
     const float prev = src ? mx[1] : mx[0];
     const float assumed = prev > 0.f ? prev : hist[2 * kHistArray + 2 + src];
     const float s = scale_for(assumed * kHistMargin);
-    if (blockIdx.x == 0 && threadIdx.x == 0) { scale_out[0] = s; hist[2 * kHistArray + 2 + (1 - src)] = assumed; }
-    float m = 0.f;
-    f32x4 cs = {0.f, 0.f, 0.f, 0.f};
-    for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-        f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * i);
-        cs += v;                                   // (the bias gradient's column sums are of the tensor as given, as in conv_absmax_kernel)
-        v = split_act(v, relu, slope);
-        m = fmaxf(fmaxf(m, fabsf(v[0])), fmaxf(fabsf(v[1]), fmaxf(fabsf(v[2]), fabsf(v[3]))));
-        v = v * s;
-        f16x4 h, l;
-        #pragma unroll
-        for (int j = 0; j < 4; ++j) { h[j] = (_Float16)v[j]; l[j] = (_Float16)(v[j] - (float)h[j]); }
-        *reinterpret_cast<f16x4*>(hi + 4 * i) = h;
-        *reinterpret_cast<f16x4*>(lo + 4 * i) = l;
-    }
+    if (bid == 0 && threadIdx.x == 0) { scale_out[0] = s; hist[2 * kHistArray + 2 + (1 - src)] = assumed; }
+    return HistPick{src, tag, s};
+}
+
+// one float4 of the (activated) tensor: its part of the workgroup's maximum, its two plane entries
+__device__ __forceinline__ float conv_split_elem(f32x4 v, float m, const float s, _Float16* __restrict__ hi, _Float16* __restrict__ lo, const int64_t i)
+{
+    m = fmaxf(fmaxf(m, fabsf(v[0])), fmaxf(fabsf(v[1]), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+    v = v * s;
+    f16x4 h, l;
+    #pragma unroll
+    for (int j = 0; j < 4; ++j) { h[j] = (_Float16)v[j]; l[j] = (_Float16)(v[j] - (float)h[j]); }
+    *reinterpret_cast<f16x4*>(hi + 4 * i) = h;
+    *reinterpret_cast<f16x4*>(lo + 4 * i) = l;
+    return m;
+}
+
+// publish: the workgroup's (maximum, tag) pair into the OTHER array, its partial row of the column sums
+__device__ __forceinline__ void conv_hist_publish(float m, const f32x4 cs, const HistPick pk, float* __restrict__ hist, float* __restrict__ colsum,
+                                                  int c4n, const unsigned bid, float* red, f32x4* red4)
+{
+    typedef float f32x2h __attribute__((ext_vector_type(2)));
     #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     if (colsum) red4[threadIdx.x] = cs;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const f32x2h p = {fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), __builtin_bit_cast(float, tag)};
-        *reinterpret_cast<f32x2h*>(hist + (1 - src) * kHistArray + 2 * blockIdx.x) = p;       // one 8-byte store: the pair is never torn
+        const f32x2h p = {fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), __builtin_bit_cast(float, pk.tag)};
+        *reinterpret_cast<f32x2h*>(hist + (1 - pk.src) * kHistArray + 2 * bid) = p;       // one 8-byte store: the pair is never torn
     }
     if (colsum && (int)threadIdx.x < c4n) {
         f32x4 t = red4[threadIdx.x];
         for (int p = threadIdx.x + c4n; p < 256; p += c4n) t += red4[p];
-        *reinterpret_cast<f32x4*>(colsum + (int64_t)blockIdx.x * 4 * c4n + 4 * threadIdx.x) = t;
+        *reinterpret_cast<f32x4*>(colsum + (int64_t)bid * 4 * c4n + 4 * threadIdx.x) = t;
     }
 }
+
+__global__ __launch_bounds__(256) void conv_split_hist_kernel(const float* __restrict__ x, int64_t n4, int relu, _Float16* __restrict__ hi,
+                                                              _Float16* __restrict__ lo, float* __restrict__ scale_out,
+                                                              float* __restrict__ hist, float* __restrict__ colsum, int c4n,
+                                                              float slope = 0.f)
+{
+    __shared__ float red[4];
+    __shared__ f32x4 red4[256];
+    const HistPick pk = conv_hist_pick(hist, scale_out, blockIdx.x);
+    float m = 0.f;
+    f32x4 cs = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * i);
+        cs += v;                                   // (the bias gradient's column sums are of the tensor as given, as in conv_absmax_kernel)
+        v = split_act(v, relu, slope);
+        m = conv_split_elem(v, m, pk.s, hi, lo, i);
+    }
+    conv_hist_publish(m, cs, pk, hist, colsum, c4n, blockIdx.x, red, red4);
+}
+
+// ---- a k-split's finish that goes on to do what the next launch did (the critic at 8x8: conv._CriticBlock) ----------------------------------
+// The convolutions of the critic's 128-channel blocks at 8x8 (and the DOWN block's conv2) share their tap loop over workgroups; an
+// elementwise launch sums the shares and writes fp32 -- and the very next launch read that tensor back only to re-express it: as the next
+// convolution's fp16 planes, or, with the block's other branch, as the block input's gradient.  4 MiB streams in under 2 us; each of
+// these launches costs 4-8 us on a dependent chain.  Here the finish does the follower's work on the value it holds:
+//   SPLIT   (forward)   y = finish(+ res) in fp32 AND the planes of relu(y) for the convolution that reads it: conv1's finish -> conv2's
+//                       input, conv2's finish (with the residual) -> the next block's conv1 input.  y stays (masks, hooks, the shortcut).
+//   MASKED  (backward)  dh = finish in fp32 AND the planes of dh * (h > 0) for conv1's backward, with the bias gradient's partial rows of
+//                       the masked values (gp_split_hist_kernel's work, csrc/wc_gp.hip; wc_mask.h holds the shared expressions).
+//   DX      (backward)  out = (x > 0 ? finish : 0) + other, the SAME block's input gradient: conv1's data gradient never reaches memory.
+// SPLIT and MASKED run on kAmaxBlocks workgroups, as the split kernels always do: workgroup b owns pair b of the reader's record and row
+// b of the partial rows, thread t visits the float4s the split's thread t visited, in its order -- the finish is a function of the
+// element alone, so regridding it changes nothing.  Every expression comes from the function the two-launch route calls: same bits.
+enum { kTailSplit = 1, kTailMasked = 2, kTailDx = 3 };
+struct FinishTailArgs {
+    KsplitReduceArgs k;                             // the finish (k.y: the fp32 output of SPLIT and MASKED; unused by DX)
+    const float* res;                               // SPLIT: the residual operand (nullable)
+    const float* mask;                              // MASKED: conv1's output h; DX: the block input x
+    const float* other;                             // DX: the block's output gradient
+    float* out;                                     // DX: the block input's gradient
+    _Float16* hi; _Float16* lo; float* scale_out; float* hist;      // SPLIT, MASKED: the reader's planes, scale word and record
+    float* colsum; int c4n;                         // MASKED: the partial rows (nullable)
+};
+
+template <bool MASKED>
+__device__ __forceinline__ void conv_finish_split_body(const FinishTailArgs& a, const unsigned bid)
+{
+    __shared__ float red[4];
+    __shared__ f32x4 red4[256];
+    const HistPick pk = conv_hist_pick(a.hist, a.scale_out, bid);
+    const float inv = 1.0f / (a.k.xscale[0] * a.k.wscale[0]);
+    float m = 0.f;
+    f32x4 cs = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t i = bid * 256 + threadIdx.x; i < a.k.n4; i += (int64_t)kAmaxBlocks * 256) {
+        f32x4 v = conv_ksplit_finish_elem(a.k.partial, a.k.ksplit, a.k.n4, a.k.cout, inv, a.k.bias, a.k.relu, a.res, i);
+        *reinterpret_cast<f32x4*>(a.k.y + 4 * i) = v;
+        if (MASKED) {
+            v = wc_mask_apply(v, *reinterpret_cast<const f32x4*>(a.mask + 4 * i), 0.f);
+            cs = wc_colsum_add(cs, v);
+        } else {
+            v = split_act(v, 1, 0.f);
+        }
+        m = conv_split_elem(v, m, pk.s, a.hi, a.lo, i);
+    }
+    conv_hist_publish(m, cs, pk, a.hist, MASKED ? a.colsum : nullptr, a.c4n, bid, red, red4);
+}
+
+__device__ __forceinline__ void conv_finish_dx_body(const FinishTailArgs& a, const unsigned bid, const unsigned nblocks)
+{
+    const float inv = 1.0f / (a.k.xscale[0] * a.k.wscale[0]);
+    for (int64_t i = (int64_t)bid * 256 + threadIdx.x; i < a.k.n4; i += (int64_t)nblocks * 256) {
+        const f32x4 d = conv_ksplit_finish_elem(a.k.partial, a.k.ksplit, a.k.n4, a.k.cout, inv, a.k.bias, a.k.relu, nullptr, i);
+        const f32x4 x = *reinterpret_cast<const f32x4*>(a.mask + 4 * i);
+        const f32x4 o = *reinterpret_cast<const f32x4*>(a.other + 4 * i);
+        *reinterpret_cast<f32x4*>(a.out + 4 * i) = conv_block_dx_elem<false>(d, x, o);
+    }
+}
+
+template <int KIND>
+__device__ __forceinline__ void conv_finish_tail_body(const FinishTailArgs& a, const unsigned bid, const unsigned nblocks)
+{
+    if (KIND == kTailDx) conv_finish_dx_body(a, bid, nblocks);
+    else conv_finish_split_body<KIND == kTailMasked>(a, bid);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void conv_finish_tail_kernel(FinishTailArgs a) { conv_finish_tail_body<KIND>(a, blockIdx.x, gridDim.x); }
 
 // ---- the history-scaled split's gated second pass (round 6) ---------------------------------------------------------------------------
 // The launch above trusts the previous call's maximum.  Three things can make that wrong: the previous tensor was all zero (nothing to
@@ -1073,6 +1185,15 @@ __global__ __launch_bounds__(256) void conv_pair_reduce_kernel(WrwReduceArgs r, 
     if ((int)blockIdx.x < wrw_blocks) conv_wrw_reduce_body(r, blockIdx.x);
     else conv_ksplit_reduce_body(k.partial, k.ksplit, k.n4, k.cout, k.xscale, k.wscale, k.bias, k.relu, k.y,
                                  blockIdx.x - wrw_blocks, gridDim.x - wrw_blocks);
+}
+
+// the same launch with the data gradient's finish going on to its follower's work (conv_finish_tail_body): kAmaxBlocks workgroups behind
+// the weight reduction's for MASKED, conv_pair_reduce_kernel's count for DX.  A kernel of its own: the one above keeps its code.
+template <int KIND>
+__global__ __launch_bounds__(256) void conv_pair_reduce_tail_kernel(WrwReduceArgs r, FinishTailArgs a, int wrw_blocks)
+{
+    if ((int)blockIdx.x < wrw_blocks) conv_wrw_reduce_body(r, blockIdx.x);
+    else conv_finish_tail_body<KIND>(a, blockIdx.x - wrw_blocks, gridDim.x - wrw_blocks);
 }
 
 // ---- weight and bias gradient of a convolution with a handful of INPUT channels (round 5) ---------------------------------------------
@@ -1704,6 +1825,77 @@ int wc_conv_res_f16x3(const void* xhi, const void* xlo, const float* xscale, con
     return (int)hipGetLastError();
 }
 
+// ---- a k-split finish with its follower's work (conv_finish_tail_kernel): wc_conv_tail_f16x3, wc_conv_bwd_pair_tail_f16x3 ----------------
+int wc_conv_tail_supported(const wc_conv_geom* g)
+{
+    return wc_conv_res_supported(g);                // a shared tap loop (so there IS a finish launch) on 128-wide tiles
+}
+
+// the tail's own operands against the convolution's output [N][Hout][Wout][Cout] -> the finish launch's argument block
+static int tail_prepare(FinishTailArgs& f, const wc_conv_tail* t, const ConvArgs& a, const wc_conv_geom* g, const float* xscale,
+                        const float* wscale, const float* bias, float* y, const void* ws)
+{
+    if (!t) return WC_ERR_NULL;
+    if (!wc_conv_tail_supported(g)) return WC_ERR_SHAPE;
+    memset(&f, 0, sizeof(f));
+    f.k.n4 = (int64_t)g->N * g->Hout * g->Wout * g->Cout / 4;
+    f.k.partial = (const float*)ws; f.k.ksplit = a.ksplit; f.k.cout = g->Cout;
+    f.k.xscale = xscale; f.k.wscale = wscale; f.k.bias = bias; f.k.relu = 0; f.k.y = y;
+    if (t->kind == WC_CONV_TAIL_DX) {
+        if (!t->mask || !t->other || !t->out) return WC_ERR_NULL;
+        if (t->out == t->mask || t->out == t->other) return WC_ERR_ARG;
+        f.mask = t->mask; f.other = t->other; f.out = t->out;
+        return WC_OK;
+    }
+    if (t->kind != WC_CONV_TAIL_SPLIT && t->kind != WC_CONV_TAIL_MASKED) return WC_ERR_ARG;
+    if (!y || !t->hi || !t->lo || !t->scale || !t->hist) return WC_ERR_NULL;
+    f.hi = (_Float16*)t->hi; f.lo = (_Float16*)t->lo; f.scale_out = t->scale; f.hist = t->hist;
+    if (t->kind == WC_CONV_TAIL_SPLIT) { f.res = t->res; return WC_OK; }
+    if (!t->mask) return WC_ERR_NULL;
+    f.mask = t->mask;
+    if (t->colsum_partials) {                       // (split_hist's rule: a thread of the 512 x 256 grid always sees the same 4 channels)
+        if (t->C != g->Cout || (t->C & 3) || 256 % (t->C >> 2) != 0) return WC_ERR_SHAPE;
+        f.colsum = t->colsum_partials; f.c4n = t->C >> 2;
+    }
+    return WC_OK;
+}
+
+// the gated second pass of a SPLIT or MASKED tail: the launches wc_conv_split_hist_f32 / wc_conv_split_hist_masked_f32 put behind theirs
+static int tail_redo(const wc_conv_tail* t, const FinishTailArgs& f, hipStream_t st)
+{
+    if (t->kind == WC_CONV_TAIL_DX || !t->redo) return WC_OK;
+    const int64_t n4 = f.k.n4;
+    if (t->kind == WC_CONV_TAIL_MASKED)
+        return wc_conv_split_redo_masked_f32(f.k.y, f.mask, 4 * n4, 0.f, t->hi, t->lo, t->scale, t->hist, (wc_stream_t)st);
+    const unsigned g2 = grid_for(n4) < 64u ? grid_for(n4) : 64u;
+    hipLaunchKernelGGL(conv_split_redo_kernel, dim3(g2), dim3(256), 0, st, (const float*)f.k.y, n4, 1, f.hi, f.lo, f.scale_out, f.hist, 0.f);
+    return (int)hipGetLastError();
+}
+
+int wc_conv_tail_f16x3(const void* xhi, const void* xlo, const float* xscale, const void* wimage, const float* wscale,
+                       const float* bias, const void* zero_line, const wc_conv_geom* g, float* y,
+                       void* ws, size_t ws_bytes, const wc_conv_tail* tail, wc_stream_t stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (!tail) return WC_ERR_NULL;
+    ConvArgs a;
+    if (tail->kind == WC_CONV_TAIL_DX && !tail->out) return WC_ERR_NULL;
+    float* y_or_out = tail->kind == WC_CONV_TAIL_DX ? tail->out : y;        // (DX: no fp32 copy of the convolution's own output)
+    const int rc = conv_prepare(a, xhi, xlo, xscale, wimage, wscale, bias, zero_line, g, 0, y_or_out, ws, ws_bytes);
+    if (rc != WC_OK) return rc;
+    FinishTailArgs f;
+    const int rt = tail_prepare(f, tail, a, g, xscale, wscale, bias, y, ws);
+    if (rt != WC_OK) return rt;
+    const hipError_t e = (g->Cout % 256) == 0 ? launch_conv<2, 4, true>(a, st) : launch_conv<2, 2, true>(a, st);
+    if (e != hipSuccess) return (int)e;
+    if (tail->kind == WC_CONV_TAIL_SPLIT) hipLaunchKernelGGL((conv_finish_tail_kernel<kTailSplit>), dim3(kAmaxBlocks), dim3(256), 0, st, f);
+    else if (tail->kind == WC_CONV_TAIL_MASKED) hipLaunchKernelGGL((conv_finish_tail_kernel<kTailMasked>), dim3(kAmaxBlocks), dim3(256), 0, st, f);
+    else hipLaunchKernelGGL((conv_finish_tail_kernel<kTailDx>), dim3(grid_for(f.k.n4)), dim3(256), 0, st, f);
+    const hipError_t e2 = hipGetLastError();
+    if (e2 != hipSuccess) return (int)e2;
+    return tail_redo(tail, f, st);
+}
+
 int wc_conv_block_dx_f32(const float* dx1, const float* x, const float* other, int64_t N, int64_t H, int64_t W, int C, int down,
                          float* out, wc_stream_t stream)
 {
@@ -1970,16 +2162,24 @@ size_t wc_conv_bwd_pair_workspace_bytes(const wc_conv_geom* gd, const wc_conv_ge
     return wc_conv_workspace_bytes(gd) + wc_conv_wrw_workspace_bytes(gf);
 }
 
-int wc_conv_bwd_pair_f16x3(const void* ghi, const void* glo, const float* gscale, const void* wimage, const float* wscale,
-                           const void* zero_line, const wc_conv_geom* gd, float* dx, void* ws_dx, size_t ws_dx_bytes,
-                           const void* xhi, const void* xlo, const float* xscale, const wc_conv_geom* gf, float* dw,
-                           int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
-                           const float* colsum_partials, float* db, void* ws_dw, size_t ws_dw_bytes, wc_stream_t stream)
+// tail == nullptr: wc_conv_bwd_pair_f16x3; else the data gradient's finish goes on to the tail's work (MASKED or DX; dx unused by DX)
+static int bwd_pair(const void* ghi, const void* glo, const float* gscale, const void* wimage, const float* wscale,
+                    const void* zero_line, const wc_conv_geom* gd, float* dx, void* ws_dx, size_t ws_dx_bytes,
+                    const void* xhi, const void* xlo, const float* xscale, const wc_conv_geom* gf, float* dw,
+                    int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
+                    const float* colsum_partials, float* db, void* ws_dw, size_t ws_dw_bytes, const wc_conv_tail* tail, hipStream_t st)
 {
-    hipStream_t st = (hipStream_t)stream;
     ConvArgs d;
-    int rc = conv_prepare(d, ghi, glo, gscale, wimage, wscale, nullptr, zero_line, gd, 0, dx, ws_dx, ws_dx_bytes);
+    if (tail && tail->kind == WC_CONV_TAIL_DX && !tail->out) return WC_ERR_NULL;
+    float* dx_or_out = (tail && tail->kind == WC_CONV_TAIL_DX) ? tail->out : dx;
+    int rc = conv_prepare(d, ghi, glo, gscale, wimage, wscale, nullptr, zero_line, gd, 0, dx_or_out, ws_dx, ws_dx_bytes);
     if (rc != WC_OK) return rc;
+    FinishTailArgs f;
+    if (tail) {
+        if (tail->kind != WC_CONV_TAIL_MASKED && tail->kind != WC_CONV_TAIL_DX) return WC_ERR_ARG;
+        rc = tail_prepare(f, tail, d, gd, gscale, wscale, nullptr, dx, ws_dx);
+        if (rc != WC_OK) return rc;
+    }
     WrwPlan p;
     rc = wrw_prepare(p, xhi, xlo, xscale, ghi, glo, gscale, zero_line, gf, dw, stride_k, stride_n, stride_r, stride_s,
                      colsum_partials, db, ws_dw, ws_dw_bytes);
@@ -2006,6 +2206,15 @@ int wc_conv_bwd_pair_f16x3(const void* ghi, const void* glo, const float* gscale
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     const int reduce_blocks = p.r.main_blocks + p.extra;
+    if (tail) {                                     // (tail_prepare took the geometry: d.ksplit > 1)
+        if (tail->kind == WC_CONV_TAIL_MASKED)
+            hipLaunchKernelGGL((conv_pair_reduce_tail_kernel<kTailMasked>), dim3(reduce_blocks + kAmaxBlocks), dim3(256), 0, st, p.r, f, reduce_blocks);
+        else
+            hipLaunchKernelGGL((conv_pair_reduce_tail_kernel<kTailDx>), dim3(reduce_blocks + grid_for(f.k.n4)), dim3(256), 0, st, p.r, f, reduce_blocks);
+        e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+        return tail_redo(tail, f, st);
+    }
     if (d.ksplit > 1) {
         KsplitReduceArgs k;
         k.n4 = (int64_t)gd->N * gd->Hout * gd->Wout * gd->Cout / 4;
@@ -2016,6 +2225,28 @@ int wc_conv_bwd_pair_f16x3(const void* ghi, const void* glo, const float* gscale
         hipLaunchKernelGGL(conv_wrw_reduce_kernel, dim3(reduce_blocks), dim3(256), 0, st, p.r);
     }
     return (int)hipGetLastError();
+}
+
+int wc_conv_bwd_pair_f16x3(const void* ghi, const void* glo, const float* gscale, const void* wimage, const float* wscale,
+                           const void* zero_line, const wc_conv_geom* gd, float* dx, void* ws_dx, size_t ws_dx_bytes,
+                           const void* xhi, const void* xlo, const float* xscale, const wc_conv_geom* gf, float* dw,
+                           int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
+                           const float* colsum_partials, float* db, void* ws_dw, size_t ws_dw_bytes, wc_stream_t stream)
+{
+    return bwd_pair(ghi, glo, gscale, wimage, wscale, zero_line, gd, dx, ws_dx, ws_dx_bytes, xhi, xlo, xscale, gf, dw,
+                    stride_k, stride_n, stride_r, stride_s, colsum_partials, db, ws_dw, ws_dw_bytes, nullptr, (hipStream_t)stream);
+}
+
+int wc_conv_bwd_pair_tail_f16x3(const void* ghi, const void* glo, const float* gscale, const void* wimage, const float* wscale,
+                                const void* zero_line, const wc_conv_geom* gd, float* dx, void* ws_dx, size_t ws_dx_bytes,
+                                const void* xhi, const void* xlo, const float* xscale, const wc_conv_geom* gf, float* dw,
+                                int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
+                                const float* colsum_partials, float* db, void* ws_dw, size_t ws_dw_bytes,
+                                const wc_conv_tail* tail, wc_stream_t stream)
+{
+    if (!tail) return WC_ERR_NULL;
+    return bwd_pair(ghi, glo, gscale, wimage, wscale, zero_line, gd, dx, ws_dx, ws_dx_bytes, xhi, xlo, xscale, gf, dw,
+                    stride_k, stride_n, stride_r, stride_s, colsum_partials, db, ws_dw, ws_dw_bytes, tail, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 //
 // Stream-ordered, no allocation, no atomics, plain vector stores.
 #include "wc_common.h"
+#include "wc_mask.h"
 #include "../../include/wc_hip.h"
 
 namespace {
@@ -23,11 +24,9 @@ constexpr int kHistRedoWord = 2 * kHistArray;
 
 __device__ __forceinline__ f32x4 masked_load(const float* __restrict__ t, const float* __restrict__ a, int64_t i, float slope)
 {
-    f32x4 v = *reinterpret_cast<const f32x4*>(t + 4 * i);
+    const f32x4 v = *reinterpret_cast<const f32x4*>(t + 4 * i);
     const f32x4 p = *reinterpret_cast<const f32x4*>(a + 4 * i);
-    #pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = v[j] * (p[j] > 0.f ? 1.0f : slope);      // (a NaN or -0 pre-activation takes the slope, as torch's a > 0)
-    return v;
+    return wc_mask_apply(v, p, slope);             // (wc_mask.h: shared with the critic's k-split finish, wc_conv.hip)
 }
 
 __device__ __forceinline__ float absmax4(float m, f32x4 v)
@@ -64,9 +63,7 @@ __device__ __forceinline__ float wave_max(float m)
 // split), in conv_absmax_kernel's / conv_split_hist_kernel's grid, stride and LDS fold (wc_conv.hip): the rows have their bits
 __device__ __forceinline__ f32x4 colsum_add(f32x4 cs, f32x4 v)
 {
-    #pragma unroll
-    for (int j = 0; j < 4; ++j) cs[j] = __fadd_rn(cs[j], v[j]);      // (never contracted with the mask's multiply)
-    return cs;
+    return wc_colsum_add(cs, v);                   // (wc_mask.h)
 }
 
 __device__ __forceinline__ void colsum_fold(f32x4* red4, float* __restrict__ colsum, int c4n)
@@ -307,6 +304,18 @@ int wc_conv_split_hist_masked_f32(const float* t, const float* a, int64_t n, flo
         const unsigned g2 = grid_for(n / 4) < 64 ? grid_for(n / 4) : 64u;
         hipLaunchKernelGGL(gp_split_redo_kernel, dim3(g2), dim3(256), 0, st, t, a, n / 4, slope, (_Float16*)hi, (_Float16*)lo, scale, hist);
     }
+    return (int)hipGetLastError();
+}
+
+// the gated second pass alone, as wc_conv_split_hist_masked_f32 launches it behind its split: for a launch that wrote the masked planes and the
+// record itself (the critic's k-split finish, wc_conv_tail_f16x3 / wc_conv_bwd_pair_tail_f16x3 in wc_conv.hip)
+int wc_conv_split_redo_masked_f32(const float* t, const float* a, int64_t n, float slope, void* hi, void* lo, float* scale, float* hist,
+                                  wc_stream_t stream)
+{
+    if (!t || !a || !hi || !lo || !scale || !hist || n <= 0 || (n & 3)) return WC_ERR_ARG;
+    if (!(slope >= 0.f && slope <= 1.f)) return WC_ERR_ARG;
+    const unsigned g2 = grid_for(n / 4) < 64 ? grid_for(n / 4) : 64u;
+    hipLaunchKernelGGL(gp_split_redo_kernel, dim3(g2), dim3(256), 0, (hipStream_t)stream, t, a, n / 4, slope, (_Float16*)hi, (_Float16*)lo, scale, hist);
     return (int)hipGetLastError();
 }
 

@@ -51,26 +51,51 @@ class ResBlockDown(nn.Module):
     def _fused_plans(self, x):
         """The three convolutions' plans when the block runs as one autograd node (conv.critic_block), else None: _fusable(), a dense fp32
         NHWC input on the GPU, shapes the convolution kernel takes."""
-        from . import conv as fc, generator as _g
+        from . import generator as _g
         if not self._fusable():
             return None
         if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
                 and getattr(x, '_wc_planes', None) is None and _g.split_of(x) is None):
             return None
-        return fc.critic_block_plans(tuple(x.shape), tuple(self.conv1.conv.weight.shape), tuple(self.conv2.conv.weight.shape),
+        return self._plans_of(tuple(x.shape))
+
+    def _plans_of(self, xshape):
+        from . import conv as fc
+        return fc.critic_block_plans(xshape, tuple(self.conv1.conv.weight.shape), tuple(self.conv2.conv.weight.shape),
                                      tuple(self.shortcut.conv.weight.shape) if self.has_shortcut else None, self.resample == 'DOWN')
 
-    def forward(self, x, cls):
+    def takes_input_planes(self, xshape):
+        """Would this block, given a dense fp32 GPU tensor of this NHWC shape that the block in front has just written, run as the fused
+        node -- so that the block in front may split it for conv1 (conv.critic_block's next_site) and hand the planes over?"""
+        return self._fusable() and self._plans_of(tuple(xshape)) is not None
+
+    def forward(self, x, cls, x_planes=None, handover=None):
+        """x_planes: the planes of relu(x) for conv1, handed over by the block in front (only ever with a block that said
+        takes_input_planes).  handover: a dict {'next': the block behind this one}; the block leaves its output's planes for that block's
+        conv1 under 'planes' when its conv2 wrote them, else None.  A block given a handover runs inside the critic's pass: the finishes of its
+        data gradients then take over their followers' launches too (conv.critic_block's backward_tails)."""
+        if handover is not None:
+            handover['planes'] = None
         plans = self._fused_plans(x)
         if plans is not None:
             from . import conv as fc
             w1, w2 = self.conv1._weight(), self.conv2._weight()
             ws = self.shortcut._weight() if self.has_shortcut else None
             x = self.bn1(x, cls)        # the identity (_fused_plans checked): called so that a forward hook on the site sees its tensor
-            y, h = fc.critic_block(x, w1, self.conv1.conv.bias, w2, self.conv2.conv.bias, ws, self.shortcut.conv.bias if self.has_shortcut else None,
-                                   (self.conv1, self.conv2, self.shortcut if self.has_shortcut else None), plans, self.resample == 'DOWN')
+            nxt = handover.get('next') if handover is not None else None
+            g2 = plans[1].fwd[0]
+            next_site = None
+            if isinstance(nxt, ResBlockDown) and nxt.takes_input_planes((g2.N, g2.Hout, g2.Wout, g2.Cout)):
+                next_site = nxt.conv1
+            y, h, planes = fc.critic_block(x, w1, self.conv1.conv.bias, w2, self.conv2.conv.bias, ws, self.shortcut.conv.bias if self.has_shortcut else None,
+                                           (self.conv1, self.conv2, self.shortcut if self.has_shortcut else None), plans, self.resample == 'DOWN',
+                                           next_site=next_site, x_planes=x_planes, backward_tails=handover is not None)
+            if handover is not None:
+                handover['planes'] = planes
             self.bn2(h, cls)            # likewise
             return y
+        if x_planes is not None:
+            raise RuntimeError("ResBlockDown: planes handed to a block that does not run as the fused node")
         # relu -> conv as one layer call: on the fast path the ReLU happens while the activation is split
         h = self.conv1(x) if self.is_first else self.conv1.forward_relu(self.bn1(x, cls))
         h = self.bn2(h, cls)
@@ -174,9 +199,15 @@ class Discriminator(nn.Module):
         if batch:                           # ... and all the block convolutions' weight images in one (conv.prepare_images)
             fc.prepare_images(self, fc.pass_key(self, x))
         try:
-            y = x
-            for blk in self.blocks:
-                y = blk(y, cls)
+            y, planes = x, None
+            for i, blk in enumerate(self.blocks):
+                if isinstance(blk, ResBlockDown):
+                    # consecutive fused blocks: conv2's finish of one writes conv1's input planes of the next (conv.critic_block)
+                    box = {'next': self.blocks[i + 1] if i + 1 < len(self.blocks) else None}
+                    y = blk(y, cls, x_planes=planes, handover=box)
+                    planes = box['planes']
+                else:
+                    y = blk(y, cls)
         finally:
             if batch:
                 fc.finish_images(self)
