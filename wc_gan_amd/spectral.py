@@ -52,6 +52,7 @@ class SpectralNormBatchFunction(torch.autograd.Function):
             saved += [w_sn, uu, vv, sigma]
         ctx.save_for_backward(*saved)
         ctx.wss, ctx.fully_diff, ctx.n = wss, bool(fully_diff), len(mods)
+        ctx.set_materialize_grads(False)      # a layer the forward left out: its gradient stays None (not zeros the backward would carry through a launch)
         return tuple(o[0] for o in outs)
 
     @staticmethod
