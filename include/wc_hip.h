@@ -561,6 +561,14 @@ typedef struct {
  * beyond a multiple of 128 -- the DC critic's 64-filter layers, discriminator.py:41-60 with arch 'dcgan' -- runs 64-output tiles). */
 int wc_conv_supported(const wc_conv_geom* g);
 
+/* 1 for every geometry wc_conv_supported takes, and for the same geometries with N*H*W a multiple of 32 instead of 128 (below 2^31 - 128):
+ * the launch runs ceil(N*H*W / 128) of the 128-point tiles, and the 32, 64 or 96 rows the last one has past the grid read zeros and
+ * write nothing -- never the 256-point tile.  This is the set the launch entries (wc_conv_f16x3, _res_, _tail_, wc_conv_wrw_*_f16x3,
+ * wc_conv_bwd_pair_*) accept, and wc_conv_res_supported / _tail_supported / _bwd_pair_supported answer for such a geometry under their
+ * own rules, with tiles counted as ceil(N*H*W / 128); wc_conv_supported keeps its value (whole tiles only), which is what a caller that
+ * has not opted in asks (wc_gan_amd/conv.py: a layer built with ragged_conv=True asks this one). */
+int wc_conv_ragged_supported(const wc_conv_geom* g);
+
 /* hi = fp16(s*x), lo = fp16(s*x - hi) over n floats (n % 4 == 0), s = the power of two that puts max|x| into
  * [2^13, 2^14) (written to *scale on the device); relu != 0 clamps at zero first.  `amax_scratch`: WC_CONV_SCRATCH_BYTES
  * device bytes (per-workgroup maxima; no atomics, nothing to clear). */

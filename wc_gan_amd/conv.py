@@ -11,7 +11,10 @@
 Forward and the data gradient run on the HIP kernel (the data gradient of 'same' is a 'same', of 'down' an 'up' and of
 'up' a 'down', with the channel roles swapped in the weight image), and so does the weight gradient (pixel-major tiles
 read back through gfx950's transposing LDS read).  `relu_input` / `leaky_input` (fast_conv_or_none): the layer is conv(relu(x)) /
-conv(leaky_relu(x, slope)) and the activation happens while x is split.  Channel widths: multiples of 128, of 64 for 'down'.  No fallback inside: `supported(...)` tells the caller whether the kernel takes a shape.
+conv(leaky_relu(x, slope)) and the activation happens while x is split.  Channel widths: multiples of 128, of 64 for 'down'.  N*H*W of the virtual grid (the output's
+for 'down' / 'down3', the input's otherwise): a multiple of 128, or -- for a layer built with ragged_conv=True (`ragged=` here) -- of 32:
+the last 128-point tile is then partial.  No fallback inside: `supported(...)` tells the caller whether the
+kernel takes a shape.
 """
 from __future__ import annotations
 
@@ -99,12 +102,18 @@ def _supported(g):
     return bool(_lib.load().wc_conv_supported(ctypes.addressof(g)))
 
 
-def supported(x, w, kind):
-    """Does the kernel take this call?  (channels multiples of 128 -- of 64 for kind 'down' --, N*H*W of the virtual grid a multiple of 128)"""
+def _ragged(site):
+    """Has the layer object opted in to a partial last tile (make_generator / make_discriminator(ragged_conv=True))?"""
+    return bool(getattr(site, 'ragged_conv', False))
+
+
+def supported(x, w, kind, ragged=False):
+    """Does the kernel take this call?  (channels multiples of 128 -- of 64 for kind 'down' --, N*H*W of the virtual grid a multiple of 128;
+    ragged, the opt-in of a layer marked ragged_conv: a multiple of 32, the last tile partial -- wc_conv_ragged_supported)"""
     handed = getattr(x, '_wc_planes', None) is not None       # a K3 handle: the data is in the planes it carries
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and (handed or x.is_contiguous()) and w.dtype == torch.float32):
         return False
-    p = _plan(kind, x, w)
+    p = _plan(kind, x, w, ragged)
     return bool(p) and p.ok
 
 
@@ -113,14 +122,16 @@ class _Plan:
     support verdict and the workspace sizes (the per-call host work is what is left: a few allocations and launches)."""
     __slots__ = ('ok', 'fwd', 'bwd', 'fwd_ws', 'bwd_ws', 'wrw_ws', 'fwd_ptr', 'bwd_ptr', 'pair', 'res', 'tail', 'bwd_tail')
 
-    def __init__(self, kind, N, H, W, wshape):
-        class _W:                                   # shape-only stand-in for the weight
+    def __init__(self, kind, N, H, W, wshape, ragged=False):
+        class _W:                                 # shape-only stand-in for the weight
             shape = wshape
         lib = _lib.load()
         (gf, kf, nf), (gb, kb, nb) = _geoms(kind, N, H, W, _W)
         self.fwd, self.bwd = (gf, kf, nf), (gb, kb, nb)
         self.fwd_ptr, self.bwd_ptr = ctypes.addressof(gf), ctypes.addressof(gb)
-        self.ok = bool(lib.wc_conv_supported(self.fwd_ptr)) and bool(lib.wc_conv_supported(self.bwd_ptr))
+        # ragged: the layer opted in to a partial last tile (N*H*W a multiple of 32); without it the answer is the one it always was
+        takes = lib.wc_conv_ragged_supported if ragged else lib.wc_conv_supported
+        self.ok = bool(takes(self.fwd_ptr)) and bool(takes(self.bwd_ptr))
         self.fwd_ws = lib.wc_conv_workspace_bytes(self.fwd_ptr) if self.ok else 0
         self.bwd_ws = lib.wc_conv_workspace_bytes(self.bwd_ptr) if self.ok else 0
         self.wrw_ws = lib.wc_conv_wrw_workspace_bytes(self.fwd_ptr) if self.ok else 0
@@ -136,8 +147,8 @@ class _Plan:
 _plans = {}
 
 
-def _plan(kind, x, w):
-    key = (kind, tuple(x.shape), tuple(w.shape))
+def _plan(kind, x, w, ragged=False):
+    key = (kind, tuple(x.shape), tuple(w.shape), bool(ragged))
     p = _plans.get(key)
     if p is None:
         N, H, W, C = x.shape
@@ -153,7 +164,7 @@ def _plan(kind, x, w):
         # tests/test_dcgan_conv_gpu.py runs them); the 64-wide ResNet blocks of toy configurations stay on their other path, as before.
         if good and kind != 'down' and (C % 128 or w.shape[0] % 128 or w.shape[1] % 128):
             good = False
-        p = _plans[key] = _Plan(kind, N, H, W, tuple(w.shape)) if good else False
+        p = _plans[key] = _Plan(kind, N, H, W, tuple(w.shape), bool(ragged)) if good else False
     return p
 
 
@@ -674,14 +685,14 @@ def backward_pair(g_planes, image, x_planes, plan, w, colsum=None, tail=None):
     return dx, dw, db
 
 
-def takes_planes(shape, wshape, kind):
+def takes_planes(shape, wshape, kind, ragged=False):
     """Would fast_conv_or_none take an input of this NHWC shape as planes handed over by K3 (functional.whiten_color(planes=True))?
-    Shapes only -- the caller asks before it runs the site."""
+    Shapes only -- the caller asks before it runs the site.  ragged: the reading layer is marked ragged_conv (see supported)."""
     class _S:
         pass
     xs, ws = _S(), _S()
     xs.shape, ws.shape = tuple(shape), tuple(wshape)
-    p = _plan(kind, xs, ws)
+    p = _plan(kind, xs, ws, ragged)
     return bool(p) and p.ok
 
 
@@ -823,7 +834,7 @@ class _SplitConv(torch.autograd.Function):
 def split_conv(x, st, w, bias=None, site=None):
     """conv1x1(x) for a handle x whose data is the ops.SplitTensor st (see _SplitConv).  Raises when the kernel does not take the
     shape -- the producer asks takes_planes() before it writes planes."""
-    p = _plan('same', x, w)
+    p = _plan('same', x, w, _ragged(site))
     if not (p and p.ok and tuple(w.shape[2:]) == (1, 1) and w.dtype == torch.float32):
         raise _lib.WcHipError(f"split_conv: a pre-split handle reached a convolution without a planes path {tuple(x.shape)} x {tuple(w.shape)}")
     return _SplitConv.apply(x, w, bias, p, st, site)
@@ -836,15 +847,16 @@ def fast_conv_or_none(x, w, bias=None, kind='same', relu_input=False, site=None,
     if leaky_input is not None and relu_input:
         raise ValueError("relu_input and leaky_input are two activations")
     handed = getattr(x, '_wc_planes', None)
-    if not supported(x, w, kind):
+    ragged = _ragged(site)                          # a layer marked ragged_conv takes a partial last tile (see supported)
+    if not supported(x, w, kind, ragged):
         if handed is not None:
             raise _lib.WcHipError(f"fast_conv: a K3 handle reached a convolution that cannot take planes {tuple(x.shape)} x {tuple(w.shape)} ({kind})")
         return None
     if handed is not None:
         if relu_input or leaky_input is not None:
             raise ValueError("a K3 handle is already ReLU'd")
-        return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w), False, handed, site)
-    return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w), relu_input, None, site,
+        return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w, ragged), False, handed, site)
+    return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w, ragged), relu_input, None, site,
                            None if leaky_input is None else float(leaky_input))
 
 
@@ -973,15 +985,16 @@ def narrow_out_wrw_supported(x, w):
     return bool(_lib.load().wc_conv_wrw_narrow_supported(N, H, W, w.shape[0], C, k))
 
 
-def fast_conv(x, w, bias=None, kind='same', residual=None):
+def fast_conv(x, w, bias=None, kind='same', residual=None, ragged=False):
     """NHWC convolution (see the module docstring) -- raises if the shape is not one the kernel takes.
     residual: a tensor of the output's shape; the result is conv(x) + residual with the bits of that sum, added in the convolution's
-    finish where the tap loop is shared over workgroups (wc_conv_res_f16x3), by an elementwise add behind the other geometries."""
-    if not supported(x, w, kind):
+    finish where the tap loop is shared over workgroups (wc_conv_res_f16x3), by an elementwise add behind the other geometries.
+    ragged: take a partial last tile (see supported)."""
+    if not supported(x, w, kind, ragged):
         raise _lib.WcHipError(f"fast_conv: unsupported call {tuple(x.shape)} x {tuple(w.shape)} ({kind})")
     if residual is None:
-        return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w))
-    return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w), False, None, None, None, residual)
+        return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w, ragged))
+    return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w, ragged), False, None, None, None, residual)
 
 
 # ---- the critic's residual block as one autograd node ------------------------------------------------------------------------------------
@@ -1003,9 +1016,10 @@ class _Shape:
         self.shape = tuple(shape)
 
 
-def critic_block_plans(xshape, w1shape, w2shape, wsshape, down):
+def critic_block_plans(xshape, w1shape, w2shape, wsshape, down, ragged=False):
     """(plan of conv1, of conv2, of the shortcut | None) when the fused block takes these shapes, else None.  Shapes only: x NHWC,
-    the weights (Cout, Cin, k, k), wsshape None for the identity shortcut, down = the block halves the grid."""
+    the weights (Cout, Cin, k, k), wsshape None for the identity shortcut, down = the block halves the grid; ragged: the block's layers
+    are marked ragged_conv (see supported)."""
     if len(xshape) != 4 or len(w1shape) != 4 or len(w2shape) != 4:
         return None
     N, H, W, C = xshape
@@ -1022,9 +1036,9 @@ def critic_block_plans(xshape, w1shape, w2shape, wsshape, down):
     if not (_colsum_ok(F1) and _colsum_ok(F2)):          # the bias gradients ride on the splits: no masked fp32 tensor to sum
         return None
     out = (N, H // 2, W // 2) if down else (N, H, W)
-    p1 = _plan('same', _Shape(xshape), _Shape(w1shape))
-    p2 = _plan('down3' if down else 'same', _Shape((N, H, W, F1)), _Shape(w2shape))
-    ps = _plan('same', _Shape(out + (C,)), _Shape(wsshape)) if wsshape is not None else None
+    p1 = _plan('same', _Shape(xshape), _Shape(w1shape), ragged)
+    p2 = _plan('down3' if down else 'same', _Shape((N, H, W, F1)), _Shape(w2shape), ragged)
+    ps = _plan('same', _Shape(out + (C,)), _Shape(wsshape), ragged) if wsshape is not None else None
     if not (p1 and p1.ok and p2 and p2.ok and (wsshape is None or (ps and ps.ok))):
         return None
     return p1, p2, ps

@@ -64,7 +64,9 @@ __device__ __forceinline__ void lds_dma16(const void* g, unsigned lds)
 }
 
 // (the body takes the workgroup's grid coordinates as arguments: conv_bwd_pair_kernel runs it on a range of a linear grid)
-template <int MB, int NB, bool KS>
+// RG: the grid's last tile is partial (N*H*W a multiple of 32, not of 128; conv_f16x3_ragged_kernel).  With RG = false the body is, line
+// for line, the one whole-tile grids always ran: their kernels keep their code.
+template <int MB, int NB, bool KS, bool RG = false>
 __device__ __forceinline__ void conv_f16x3_body(const ConvArgs& a, const unsigned bx, const unsigned by, const unsigned bz)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -90,6 +92,12 @@ __device__ __forceinline__ void conv_f16x3_body(const ConvArgs& a, const unsigne
         const unsigned n = __umulhi(m, a.magHW) >> a.shHW, rem = m - n * HW;
         const unsigned yy = __umulhi(rem, a.magW) >> a.shW, xx = rem - yy * a.W;
         gy[q] = yy * a.in_stride; gx[q] = xx * a.in_stride; gpix[q] = n * (a.Hin * a.Win);
+        // a partial last tile: the rows past the grid have n >= N.  Their row coordinate is put where no tap offset (a signed char) brings
+        // it back inside [0, Hin), so every tap of theirs fails the test below and reads the zero line -- decided here, once; the loop
+        // keeps its code -- and no address is formed from their n
+        if constexpr (RG) {
+            if (n >= (unsigned)a.N) { gy[q] = -1024; gpix[q] = 0; }
+        }
     }
     const unsigned lds0 = (unsigned)(size_t)((__attribute__((address_space(3))) char*)smem);
     const int nchunk = a.Cin >> 5;
@@ -228,6 +236,9 @@ __device__ __forceinline__ void conv_f16x3_body(const ConvArgs& a, const unsigne
             const unsigned m = m0 + (wm * MB + i) * 32 + row;
             const unsigned n = __umulhi(m, a.magHW) >> a.shHW, rem = m - n * HW;
             const unsigned yy = __umulhi(rem, a.magW) >> a.shW, xx = rem - yy * a.W;
+            if constexpr (RG) {
+                if (n >= (unsigned)a.N) continue;   // a row past the grid: nothing to write, to y or to the partial sums
+            }
             const int64_t opix = ((int64_t)n * a.Hout + (yy * a.out_stride + oy0)) * a.Wout + (xx * a.out_stride + ox0);
             const int64_t oe = opix * a.Cout + nt * TN + wn * NB * 32 + (lane & 31);
             if (KS) {                               // raw partial sums; conv_ksplit_reduce_kernel finishes
@@ -249,6 +260,11 @@ __device__ __forceinline__ void conv_f16x3_body(const ConvArgs& a, const unsigne
 
 template <int MB, int NB, bool KS>
 __global__ __launch_bounds__(256) void conv_f16x3_kernel(ConvArgs a) { conv_f16x3_body<MB, NB, KS>(a, blockIdx.x, blockIdx.y, blockIdx.z); }
+
+// the same tiles on a grid whose last tile along x is partial (wc_conv_ragged_supported; the 128-point tiles only): a kernel of its own, so
+// that the one above keeps its code
+template <int NB, bool KS>
+__global__ __launch_bounds__(256) void conv_f16x3_ragged_kernel(ConvArgs a) { conv_f16x3_body<2, NB, KS, true>(a, blockIdx.x, blockIdx.y, blockIdx.z); }
 
 // ---- small grids: the (tap, chunk) loop split over blockIdx.z; y = (sum of the partial sums) / (sx*sw) + bias ---------
 struct KsplitReduceArgs {
@@ -1166,17 +1182,30 @@ __global__ __launch_bounds__(256) void conv_wrw_reduce_kernel(WrwReduceArgs a) {
 //   blocks [wrw_off, ...):    the weight gradient's (split, tile) as dim3(splits, tiles) linearises; wrw_off = conv_blocks rounded up to a
 //                             multiple of 8 (the blocks between return at once), so a pixel range keeps its residue mod 8, i.e. the
 //                             workgroups that read one range still share an XCD as wrw_splits means them to.
-template <bool KS>
-__global__ __launch_bounds__(256) void conv_bwd_pair_kernel(ConvArgs d, WrwArgs w, int conv_blocks, int wrw_off, int wrw_splits, int gx, int gy)
+template <bool KS, bool RG>
+__device__ __forceinline__ void conv_bwd_pair_body(const ConvArgs& d, const WrwArgs& w, int conv_blocks, int wrw_off, int wrw_splits, int gx, int gy)
 {
     const int b = blockIdx.x;
     if (b < conv_blocks) {
         const int t = b / gx, z = t / gy;
-        conv_f16x3_body<2, 2, KS>(d, (unsigned)(b - t * gx), (unsigned)(t - z * gy), (unsigned)z);
+        conv_f16x3_body<2, 2, KS, RG>(d, (unsigned)(b - t * gx), (unsigned)(t - z * gy), (unsigned)z);
     } else if (b >= wrw_off) {
         const int e = b - wrw_off, tile = e / wrw_splits;
         conv_wrw_body<2, 2>(w, (unsigned)(e - tile * wrw_splits), (unsigned)tile);
     }
+}
+
+template <bool KS>
+__global__ __launch_bounds__(256) void conv_bwd_pair_kernel(ConvArgs d, WrwArgs w, int conv_blocks, int wrw_off, int wrw_splits, int gx, int gy)
+{
+    conv_bwd_pair_body<KS, false>(d, w, conv_blocks, wrw_off, wrw_splits, gx, gy);
+}
+
+// the data gradient's grid with a partial last tile (conv_f16x3_ragged_kernel's body); the weight gradient's part is the same
+template <bool KS>
+__global__ __launch_bounds__(256) void conv_bwd_pair_ragged_kernel(ConvArgs d, WrwArgs w, int conv_blocks, int wrw_off, int wrw_splits, int gx, int gy)
+{
+    conv_bwd_pair_body<KS, true>(d, w, conv_blocks, wrw_off, wrw_splits, gx, gy);
 }
 
 // blocks [0, wrw_blocks): conv_wrw_reduce_kernel's (main and bias-gradient blocks); the rest: conv_ksplit_reduce_kernel's
@@ -1442,9 +1471,18 @@ template <int MB, int NB, bool KS = false>
 hipError_t launch_conv(const ConvArgs& a, hipStream_t st)
 {
     constexpr int LDS = 2 * (2 * MB * 4 * 1024 + 2 * NB * 4 * 1024);
+    const int64_t M = (int64_t)a.N * a.H * a.W;
+    if constexpr (MB == 2) {
+        if (M % 128) {      // a partial last tile (wc_conv_ragged_supported): only ever on the 128-point tiles, conv_big_tile keeps M % 256 == 0
+            hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(conv_f16x3_ragged_kernel<NB, KS>), LDS);
+            if (e != hipSuccess) return e;
+            dim3 grid((unsigned)((M + 127) / 128), (unsigned)(a.nphase * (a.Cout / (64 * NB))), (unsigned)a.ksplit);
+            hipLaunchKernelGGL((conv_f16x3_ragged_kernel<NB, KS>), grid, dim3(256), LDS, st, a);
+            return hipGetLastError();
+        }
+    }
     hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(conv_f16x3_kernel<MB, NB, KS>), LDS);
     if (e != hipSuccess) return e;
-    const int64_t M = (int64_t)a.N * a.H * a.W;
     dim3 grid((unsigned)(M / (64 * MB)), (unsigned)(a.nphase * (a.Cout / (64 * NB))), (unsigned)a.ksplit);
     hipLaunchKernelGGL((conv_f16x3_kernel<MB, NB, KS>), grid, dim3(256), LDS, st, a);
     return hipGetLastError();
@@ -1709,17 +1747,29 @@ int wc_conv_absmax_batch_f32(const wc_conv_absmax_job* jobs, int count, wc_strea
     return (int)hipGetLastError();
 }
 
-int wc_conv_supported(const wc_conv_geom* g)
+// rows: what N*H*W must be a multiple of -- 128 (whole tiles: wc_conv_supported) or 32 (whole m-blocks, a partial last tile:
+// wc_conv_ragged_supported); every other rule is shared
+static int conv_geom_ok(const wc_conv_geom* g, int rows)
 {
     if (!g) return 0;
     if (g->ntaps < 1 || g->ntaps > kMaxTaps || g->nphase < 1 || g->nphase > kMaxPhase) return 0;
     if ((g->Cin & 31) || (g->Cout & 63)) return 0;    // (Cout % 128 == 64: the 64-output tile <2, 1>)
     const int64_t M = (int64_t)g->N * g->H * g->W;
-    if (M <= 0 || (M & 127) || M > (int64_t)1 << 31) return 0;
+    // (M <= 2^31 - 128: the last tile's rows past the grid stay below 2^31, where the multiply-shift division is exact)
+    if (M <= 0 || (M % rows) || M > ((int64_t)1 << 31) - (rows == 128 ? 0 : 128)) return 0;
     if ((int64_t)g->N * g->Hin * g->Win > (int64_t)1 << 31) return 0;
     if (g->W < 2 || g->H < 1) return 0;             // (the multiply-shift division wants divisors >= 2)
     return 1;
 }
+
+int wc_conv_supported(const wc_conv_geom* g) { return conv_geom_ok(g, 128); }
+
+// what the launch entries take: wc_conv_supported's set and the same geometries with N*H*W a multiple of 32 -- the last 128-point tile then
+// has 32, 64 or 96 rows, the others read zeros and write nothing (conv_f16x3_body).  wc_conv_supported keeps its value: the layer entry of
+// an unmarked layer (wc_gan_amd/conv.py) asks it.
+int wc_conv_ragged_supported(const wc_conv_geom* g) { return conv_geom_ok(g, 32); }
+
+static int64_t conv_tiles(int64_t M) { return (M + 127) / 128; }       // 128-point tiles along x, the last one partial or whole
 
 constexpr int kKsplitMaxWgs = 96;         // k-split only grids of at most this many output tiles ...
 constexpr int kKsplitTargetWgs = 256;     // ... into about this many workgroups
@@ -1730,7 +1780,7 @@ static int conv_ksplit(const wc_conv_geom* g)
     // small grids leave most CUs idle with 128-point x (128|256)-output tiles: share the (tap, chunk) loop
     const int64_t M = (int64_t)g->N * g->H * g->W;
     const bool wide = (g->Cout % 256) == 0;
-    const int64_t wgs = (M / 128) * g->nphase * (g->Cout / (wide ? 256 : (g->Cout % 128) ? 64 : 128));
+    const int64_t wgs = conv_tiles(M) * g->nphase * (g->Cout / (wide ? 256 : (g->Cout % 128) ? 64 : 128));
     const int iters = g->ntaps * (g->Cin / 32);
     if (wgs > kKsplitMaxWgs || iters < 8) return 1;
     int k = (int)((kKsplitTargetWgs + wgs - 1) / wgs);
@@ -1759,7 +1809,7 @@ static int conv_prepare(ConvArgs& a, const void* xhi, const void* xlo, const flo
                         const float* bias, const void* zero_line, const wc_conv_geom* g, int relu, float* y, void* ws, size_t ws_bytes)
 {
     if (!xhi || !xlo || !xscale || !wimage || !wscale || !zero_line || !g || !y) return WC_ERR_ARG;
-    if (!wc_conv_supported(g)) return WC_ERR_SHAPE;
+    if (!wc_conv_ragged_supported(g)) return WC_ERR_SHAPE;
     a.xhi = (const _Float16*)xhi; a.xlo = (const _Float16*)xlo; a.zero = (const _Float16*)zero_line;
     a.wimg = (const char*)wimage; a.xscale = xscale; a.wscale = wscale; a.bias = bias; a.y = y;
     a.N = g->N; a.H = g->H; a.W = g->W; a.Hin = g->Hin; a.Win = g->Win; a.Cin = g->Cin; a.Cout = g->Cout;
@@ -1804,7 +1854,7 @@ int wc_conv_f16x3(const void* xhi, const void* xlo, const float* xscale, const v
 // conv_f16x3_kernel instantiation's code) is left as it is, its caller adds the residual itself.
 int wc_conv_res_supported(const wc_conv_geom* g)
 {
-    return g && wc_conv_supported(g) && (g->Cout % 128) == 0 && conv_ksplit(g) > 1;
+    return g && wc_conv_ragged_supported(g) && (g->Cout % 128) == 0 && conv_ksplit(g) > 1;
 }
 
 int wc_conv_res_f16x3(const void* xhi, const void* xlo, const float* xscale, const void* wimage, const float* wscale,
@@ -2052,7 +2102,7 @@ static int wrw_prepare(WrwPlan& p, const void* xhi, const void* xlo, const float
                        int64_t stride_r, int64_t stride_s, const float* colsum_partials, float* db, void* ws, size_t ws_bytes)
 {
     if (!xhi || !xlo || !xscale || !ghi || !glo || !gscale || !zero_line || !g || !dw || !ws) return WC_ERR_NULL;
-    if (!wc_conv_supported(g) || (g->Cin & 63) || g->W < 2 || g->H * g->W < 2) return WC_ERR_SHAPE;
+    if (!wc_conv_ragged_supported(g) || (g->Cin & 63) || g->W < 2 || g->H * g->W < 2) return WC_ERR_SHAPE;
     if (ws_bytes < wc_conv_wrw_workspace_bytes(g)) return WC_ERR_WORKSPACE;
     if ((colsum_partials == nullptr) != (db == nullptr)) return WC_ERR_NULL;
     if (db && ((g->Cout & 3) || 256 % (g->Cout >> 2) != 0)) return WC_ERR_SHAPE;
@@ -2142,7 +2192,7 @@ int wc_conv_wrw_bias_f16x3(const void* xhi, const void* xlo, const float* xscale
 // gd = the data-gradient geometry (what wc_conv_f16x3 is given for dx), gf = the forward geometry (what wc_conv_wrw_bias_f16x3 is given).
 int wc_conv_bwd_pair_supported(const wc_conv_geom* gd, const wc_conv_geom* gf)
 {
-    if (!gd || !gf || !wc_conv_supported(gd) || !wc_conv_supported(gf) || (gf->Cin & 63) || gf->H * gf->W < 2) return 0;
+    if (!gd || !gf || !wc_conv_ragged_supported(gd) || !wc_conv_ragged_supported(gf) || (gf->Cin & 63) || gf->H * gf->W < 2) return 0;
     // one layer: the data gradient reads the planes the weight gradient takes as gy, and writes an x-shaped tensor
     if (gd->N != gf->N || gd->Cin != gf->Cout || gd->Cout != gf->Cin) return 0;
     if (gd->Hin != gf->Hout || gd->Win != gf->Wout || gd->Hout != gf->Hin || gd->Wout != gf->Win) return 0;
@@ -2187,12 +2237,24 @@ static int bwd_pair(const void* ghi, const void* glo, const float* gscale, const
     if (!wc_conv_bwd_pair_supported(gd, gf) || p.T != 128) return WC_ERR_SHAPE;
     constexpr int LDS = 2 * (2 * 2 * 4 * 1024 + 2 * 2 * 4 * 1024);
     const int64_t M = (int64_t)gd->N * gd->H * gd->W;
-    const int gx = (int)(M / 128), gy = gd->nphase * (gd->Cout / 128);          // launch_conv<2, 2>'s grid
+    const int gx = (int)conv_tiles(M), gy = gd->nphase * (gd->Cout / 128);          // launch_conv<2, 2>'s grid
     const int64_t conv_blocks = (int64_t)gx * gy * d.ksplit, wrw_off = (conv_blocks + 7) & ~(int64_t)7;
     const int64_t blocks = wrw_off + (int64_t)p.splits * p.tiles;
     if (blocks > 0x7fffffff) return WC_ERR_SHAPE;
     hipError_t e;
-    if (d.ksplit > 1) {
+    if (M % 128) {          // a partial last tile in the data gradient's grid
+        if (d.ksplit > 1) {
+            e = wc_set_max_lds(reinterpret_cast<const void*>(conv_bwd_pair_ragged_kernel<true>), LDS);
+            if (e != hipSuccess) return (int)e;
+            hipLaunchKernelGGL((conv_bwd_pair_ragged_kernel<true>), dim3((unsigned)blocks), dim3(256), LDS, st, d, p.a,
+                               (int)conv_blocks, (int)wrw_off, p.splits, gx, gy);
+        } else {
+            e = wc_set_max_lds(reinterpret_cast<const void*>(conv_bwd_pair_ragged_kernel<false>), LDS);
+            if (e != hipSuccess) return (int)e;
+            hipLaunchKernelGGL((conv_bwd_pair_ragged_kernel<false>), dim3((unsigned)blocks), dim3(256), LDS, st, d, p.a,
+                               (int)conv_blocks, (int)wrw_off, p.splits, gx, gy);
+        }
+    } else if (d.ksplit > 1) {
         e = wc_set_max_lds(reinterpret_cast<const void*>(conv_bwd_pair_kernel<true>), LDS);
         if (e != hipSuccess) return (int)e;
         hipLaunchKernelGGL((conv_bwd_pair_kernel<true>), dim3((unsigned)blocks), dim3(256), LDS, st, d, p.a,

@@ -62,7 +62,8 @@ class ResBlockDown(nn.Module):
     def _plans_of(self, xshape):
         from . import conv as fc
         return fc.critic_block_plans(xshape, tuple(self.conv1.conv.weight.shape), tuple(self.conv2.conv.weight.shape),
-                                     tuple(self.shortcut.conv.weight.shape) if self.has_shortcut else None, self.resample == 'DOWN')
+                                     tuple(self.shortcut.conv.weight.shape) if self.has_shortcut else None, self.resample == 'DOWN',
+                                     ragged=fc._ragged(self.conv1))
 
     def takes_input_planes(self, xshape):
         """Would this block, given a dense fp32 GPU tensor of this NHWC shape that the block in front has just written, run as the fused
@@ -247,12 +248,14 @@ def make_discriminator(input_image_shape=(32, 32, 3), input_cls_shape=(1,), bloc
                        resamples=('DOWN', 'DOWN', 'SAME', 'SAME'), number_of_classes=10,
                        type='AC_GAN', norm='n', after_norm='n', spectral=False,
                        fully_diff_spectral=False, spectral_iterations=1, conv_singular=True,
-                       sum_pool=False, dropout=False, arch='res', filters_emb=10, fused_tail=False, fused_projection=False):
+                       sum_pool=False, dropout=False, arch='res', filters_emb=10, fused_tail=False, fused_projection=False,
+                       ragged_conv=False):
     """Keyword surface AND defaults of discriminator.py:15-20.  The shipped recipes pass type / spectral / sum_pool
     explicitly (run.py:230-233 from --gan_type, --discriminator_spectral, --sum_pool default 1), as wc_gan_amd.train's
     configs do.  `conv_singular=True` (the reference's default here; run.py:270 passes 0) asks for the
     convolution-operator singular value of SNConv2D, which this harness does not build: it warns and uses the
-    reshaped-kernel sigma of the SN-GAN paper.  `fused_tail`, `fused_projection` (ours, default False): see Discriminator."""
+    reshaped-kernel sigma of the SN-GAN paper.  `fused_tail`, `fused_projection` (ours, default False): see Discriminator.
+    `ragged_conv` (ours, default False): marks every convolution layer -- see generator.Conv2D."""
     assert arch in ('res', 'dcgan')
     assert type in [None, 'AC_GAN', 'PROJECTIVE']
     if spectral and conv_singular:
@@ -260,7 +263,7 @@ def make_discriminator(input_image_shape=(32, 32, 3), input_cls_shape=(1,), bloc
         warnings.warn("conv_singular=True is not built: spectral normalisation uses the reshaped-kernel singular value",
                       stacklevel=2)
     sn_kw = dict(spectral_iterations=spectral_iterations, fully_diff_spectral=fully_diff_spectral)
-    conv_layer = partial(Conv2D, spectral=bool(spectral), conv_singular=conv_singular, **sn_kw)
+    conv_layer = partial(Conv2D, spectral=bool(spectral), conv_singular=conv_singular, ragged_conv=bool(ragged_conv), **sn_kw)
 
     def dense(i, o):        # SNDense / Dense (discriminator.py:29-30)
         if spectral:

@@ -106,8 +106,11 @@ class Conv2D(nn.Module):
     stride 2 (the DC critic's DOWN blocks): the 4x4 kernel only -- Keras 'same' then pads 1 and 1, torch's padding=1."""
 
     def __init__(self, in_channels, filters, kernel_size=(3, 3), use_bias=True, name=None, spectral=False,
-                 spectral_iterations=1, fully_diff_spectral=False, conv_singular=True, stride=1):
+                 spectral_iterations=1, fully_diff_spectral=False, conv_singular=True, stride=1, ragged_conv=False):
         super().__init__()
+        # ragged_conv (ours): the block kernels may take this layer at a grid whose N*H*W is a multiple of 32 but not of 128, on a partial
+        # last tile (conv.supported(ragged=True), DESIGN.md section 4.21); off, the layer keeps the routes it always had
+        self.ragged_conv = bool(ragged_conv)
         k = kernel_size if isinstance(kernel_size, int) else kernel_size[0]
         if stride not in (1, 2) or (stride == 2 and k != 4):
             raise ValueError(f"Conv2D: stride 2 is built for the 4x4 kernel ('same' = padding 1), not {k}x{k} / {stride}")
@@ -139,7 +142,7 @@ class Conv2D(nn.Module):
             return False
         if kind == 'up3' and tuple(c.weight.shape[2:]) != (3, 3):
             return False
-        return c.weight.dtype == torch.float32 and fast_conv_mod.takes_planes(shape, c.weight.shape, kind)
+        return c.weight.dtype == torch.float32 and fast_conv_mod.takes_planes(shape, c.weight.shape, kind, self.ragged_conv)
 
     def takes_split(self, shape):
         """Will forward() read an input of this NHWC shape as the pre-split planes the residual add wrote (functional.residual_add)?
@@ -147,7 +150,7 @@ class Conv2D(nn.Module):
         c = self.conv
         if not (FAST_CONV and SPLIT_PRODUCER) or tuple(c.kernel_size) != (1, 1) or c.weight.dtype != torch.float32:
             return False
-        return fast_conv_mod.takes_planes(shape, c.weight.shape, 'same')
+        return fast_conv_mod.takes_planes(shape, c.weight.shape, 'same', self.ragged_conv)
 
     def forward_relu(self, x):
         """conv(relu(x)): on the fast path the ReLU happens while the activation is split (one kernel and one pass less)"""
@@ -379,7 +382,8 @@ class ResBlockUp(nn.Module):
     def forward(self, x, cls, readers=()):
         """readers: the modules that read this block's output (the next block's bn1 and shortcut, or the generator's last norm) --
         when each of them has a planes path for the output's shape, the residual add writes pre-split planes instead of fp32."""
-        up = self.resample == 'UP' and x.shape[1] * x.shape[2] >= 64
+        # (a conv1 marked ragged_conv: the one-launch form from the MNIST recipes' 7x7 first block on -- its grid is what the flag is for)
+        up = self.resample == 'UP' and x.shape[1] * x.shape[2] >= (49 if self.conv1.ragged_conv else 64)
         h = _norm_relu(self.bn1, x, cls, self.conv1 if (up or self.resample != 'UP') else None, 'up3' if up else 'same')
         # the 1x1 shortcut commutes with nearest-neighbour upsampling (every output pixel is the same per-pixel affine
         # map of its source pixel): it runs at the input resolution, a quarter of the work, and is added per 2x2 patch below
@@ -398,7 +402,7 @@ class ResBlockUp(nn.Module):
             # from 8x8 inputs on, upsample + 3x3 as one 4x4 stride-2 transposed convolution is faster than MIOpen on
             # the 4x tensor (measured forward+backward at N = 128: 3.91 -> 2.02 ms from 16x16, 1.06 -> 0.72 from 8x8,
             # even at 4x4)
-            h = self.conv1.forward_upsampled(h) if h.shape[1] * h.shape[2] >= 64 else self.conv1(upsample2x(h))
+            h = self.conv1.forward_upsampled(h) if up else self.conv1(upsample2x(h))
         else:
             h = self.conv1(h)
         h = _norm_relu(self.bn2, h, cls, self.conv2)
@@ -428,10 +432,11 @@ class DCBlockUp(nn.Module):
     bias and no spectral norm (generator.py:148).  UP: on the 4x4 stride-2 transposed kernel of wc_gan_amd.conv ('up'), the site's
     planes handed over where K3 writes them; SAME (no recipe): a 4x4 stride-1 transposed convolution on torch."""
 
-    def __init__(self, in_ch, nfilters, resample, name, norm):
+    def __init__(self, in_ch, nfilters, resample, name, norm, ragged_conv=False):
         super().__init__()
         assert resample in ('UP', 'SAME')
         self.resample = resample
+        self.ragged_conv = bool(ragged_conv)        # (as Conv2D's: this object is the deconvolution's site)
         self.deconv = nn.ConvTranspose2d(in_ch, nfilters, 4, stride=2 if resample == 'UP' else 1,
                                          padding=1 if resample == 'UP' else 0).to(memory_format=torch.channels_last)
         self.bn = norm(axis=-1, name=name + '.bn', channels=in_ch)
@@ -440,7 +445,7 @@ class DCBlockUp(nn.Module):
         """Will forward() read an input of this shape as planes handed over by the WC site in front of the deconvolution?"""
         w = self.deconv.weight
         return (FAST_CONV and HANDOFF and self.resample == 'UP' and kind == 'up' and w.dtype == torch.float32
-                and fast_conv_mod.takes_planes(shape, w.shape, 'up'))
+                and fast_conv_mod.takes_planes(shape, w.shape, 'up', self.ragged_conv))
 
     def forward(self, x, cls):
         up = self.resample == 'UP'
@@ -456,7 +461,7 @@ class DCBlockUp(nn.Module):
 class Generator(nn.Module):
     def __init__(self, input_noise_shape, output_channels, first_block_shape, block_sizes, resamples,
                  block_norm_layer, last_norm_layer, conv_layer, dense_spectral, concat_cls, number_of_classes, arch,
-                 conditional):
+                 conditional, ragged_conv=False):
         super().__init__()
         self.first_block_shape = tuple(int(v) for v in first_block_shape)
         self.conditional = conditional
@@ -482,7 +487,7 @@ class Generator(nn.Module):
             if arch == 'res':
                 blocks.append(ResBlockUp(ch, bs, rs, name, block_norm_layer, conv_layer))
             else:
-                blocks.append(DCBlockUp(ch, bs, rs, name, block_norm_layer))
+                blocks.append(DCBlockUp(ch, bs, rs, name, block_norm_layer, ragged_conv=ragged_conv))
             ch = bs
         self.blocks = nn.ModuleList(blocks)
         self.final_norm = last_norm_layer(axis=-1, name='Generator.BN.Final', channels=ch)
@@ -514,18 +519,18 @@ def make_generator(input_noise_shape=(128,), output_channels=3, input_cls_shape=
                    block_norm='u', block_after_norm='cs', filters_emb=10,
                    last_norm='u', last_after_norm='cs', gan_type=None, arch='res',
                    spectral=False, fully_diff_spectral=False, spectral_iterations=1, conv_singular=True,
-                   process_group=None, fused_batch_norm=False, decomposition='cholesky'):
+                   process_group=None, fused_batch_norm=False, decomposition='cholesky', ragged_conv=False):
     """Same keyword surface as generator.py:93-98; returns an nn.Module called as G(z) or G(z, cls).
-    fused_batch_norm, decomposition: see create_norm."""
+    fused_batch_norm, decomposition: see create_norm.  ragged_conv (ours, default False): marks every convolution layer -- see Conv2D."""
     assert arch in ['res', 'dcgan']
     if spectral and (block_after_norm not in ('uconv', 'ucs', 'n') or last_after_norm not in ('uconv', 'ucs', 'n')):
         raise NotImplementedError("spectral-normalised conditional coloring (SNConditionalConv11/SNFactorizedConv11) "
                                   "is outside the WC hot path; no shipped recipe sets --generator_spectral")
-    conv_layer = partial(Conv2D, spectral=bool(spectral))
+    conv_layer = partial(Conv2D, spectral=bool(spectral), ragged_conv=bool(ragged_conv))
     mk = partial(create_norm, number_of_classes=number_of_classes, filters_emb=filters_emb, process_group=process_group,
                  fused_batch_norm=fused_batch_norm, decomposition=decomposition)
     block_norm_layer = mk(block_norm, block_after_norm)
     last_norm_layer = mk(last_norm, last_after_norm)
     return Generator(input_noise_shape, output_channels, first_block_shape, block_sizes, resamples,
                      block_norm_layer, last_norm_layer, conv_layer, bool(spectral), concat_cls, number_of_classes, arch,
-                     conditional=gan_type is not None)
+                     conditional=gan_type is not None, ragged_conv=bool(ragged_conv))

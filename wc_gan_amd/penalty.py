@@ -122,8 +122,9 @@ class _Layer:
         self.pad = self.w.shape[2] // 2
         self._images = None
         from . import generator as _g          # WC_FAST_CONV=0 means MIOpen everywhere: here too (the narrow layers follow conv.NARROW_WRW)
-        if _g.FAST_CONV and C.supported(x, self.w, self.kind):
-            self.route, self.plan = 'block', C._plan(self.kind, x, self.w)
+        ragged = C._ragged(layer)              # a layer marked ragged_conv takes a partial last tile here as in its own forward
+        if _g.FAST_CONV and C.supported(x, self.w, self.kind, ragged):
+            self.route, self.plan = 'block', C._plan(self.kind, x, self.w, ragged)
         elif not pooled and C.narrow_wrw_supported(x, self.w) and C._storage_extent(self.w) == self.w.numel():
             self.route = 'narrow'
         else:

@@ -573,6 +573,38 @@ PROJECTION_SCHEDULES = {
 }
 
 
+MNIST_RAGGED_SHIPS = True           # profiles/mnist_step.json: faster in every one of 7 rounds on both recipes
+
+
+def _mnist(filters, after_norm, gan_type):
+    """scripts/{mnist,fashionmnist}_resnet_sn_{uncond,cond}.sh with run.py:147-237 for a dataset whose name ends in 'mnist': one output
+    channel, a (7, 7, F) first block (run.py:152) and two UP blocks of F filters (run.py:165-166) -- 28 x 28 x 1 images --, norms d / uconv at
+    the last site, hinge objectives, the four-block critic of 128 filters with spectral normalisation and --sum_pool 1; the conditional
+    scripts add --gan_type PROJECTIVE and the block after-norm ucconv.  At the recipes' batch of 64 the 7x7 grids have N*H*W = 3136 =
+    24 * 128 + 64 (15680 in the five-round generation): the block kernels take them on a partial last tile where ragged_conv is on.
+    fused_projection stays off: the tail has not been measured at (128, 49, 128, 10)."""
+    conditional = gan_type is not None
+    return dict(
+        generator=dict(output_channels=1, block_sizes=(filters, filters), resamples=("UP", "UP"), first_block_shape=(7, 7, filters),
+                       number_of_classes=10, block_norm='d', block_after_norm=after_norm, last_norm='d', last_after_norm='uconv',
+                       gan_type=gan_type, ragged_conv=MNIST_RAGGED_SHIPS),
+        discriminator=dict(input_image_shape=(28, 28, 1), block_sizes=(128, 128, 128, 128), resamples=('DOWN', 'DOWN', 'SAME', 'SAME'),
+                           number_of_classes=10, type=gan_type, spectral=True, sum_pool=True, conv_singular=False,
+                           ragged_conv=MNIST_RAGGED_SHIPS),
+        image_shape=(28, 28, 1), conditional=conditional)
+
+
+# the four MNIST-family recipes; NOT in CONFIGS (bench.py's names), their schedules in a table of their own
+MNIST_CONFIGS = {'mnist_uncond': _mnist(256, 'uconv', None), 'mnist_cond': _mnist(128, 'ucconv', 'PROJECTIVE'),
+                 'fashionmnist_uncond': _mnist(256, 'uconv', None), 'fashionmnist_cond': _mnist(128, 'ucconv', 'PROJECTIVE')}
+MNIST_SCHEDULES = {
+    'mnist_uncond': dict(lr_decay_schedule=None, number_of_epochs=5),                   # scripts/mnist_resnet_sn_uncond.sh:7 (no schedule given)
+    'mnist_cond': dict(lr_decay_schedule=None, number_of_epochs=5),                     # scripts/mnist_resnet_sn_cond.sh:7
+    'fashionmnist_uncond': dict(lr_decay_schedule='linear', number_of_epochs=20),       # scripts/fashionmnist_resnet_sn_uncond.sh:7
+    'fashionmnist_cond': dict(lr_decay_schedule='linear', number_of_epochs=20),         # scripts/fashionmnist_resnet_sn_cond.sh:7
+}
+
+
 # --lr_decay_schedule / --number_of_epochs of each recipe's script: GanTrainer's arguments of the same names (the config tables above carry
 # the networks alone and are left as they are).  build_trainer(CONFIGS[name], **RECIPE_SCHEDULES[name]) trains the recipe at its script's rates.
 RECIPE_SCHEDULES = {
@@ -627,6 +659,17 @@ def fused_projection_config(config):
     import copy
     out = copy.deepcopy(config)
     out['discriminator'].update(fused_projection=True)
+    return out
+
+
+def ragged_config(config, on=True):
+    """The same recipe with every convolution layer of both networks marked ragged_conv (make_generator / make_discriminator(ragged_conv=
+    True)): the block kernels then take grids whose N*H*W is a multiple of 32 on a partial last tile.  A copy of any
+    entry, the entry itself is left alone; on=False gives the copy with the mark off."""
+    import copy
+    out = copy.deepcopy(config)
+    out['generator'].update(ragged_conv=bool(on))
+    out['discriminator'].update(ragged_conv=bool(on))
     return out
 
 
