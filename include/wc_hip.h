@@ -733,6 +733,34 @@ int    wc_conv_fwd_narrow_f32(const float* x, const float* w, int64_t stride_k, 
                               const float* bias /*nullable*/, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize, int relu,
                               float* y, wc_stream_t stream);
 
+/* ==== the critic's first block: conv1 writes conv2's planes, conv1's weight gradient applies the ReLU mask ==============================
+ * Additive: WC_CORE_API keeps its list and WC_ABI_VERSION its value; the entries above keep their signatures and their kernels.
+ * The first block (discriminator.py:41-54 with is_first) holds the critic's largest tensor, conv1's output h (64 MiB at 128x32x32x128).
+ *
+ * wc_conv_fwd_narrow_split_f32 = wc_conv_fwd_narrow_f32(..., relu = 0, y) followed by wc_conv_split_hist_f32(y, relu, slope, ...) on an
+ * already seeded record `hist` (WC_CONV_HIST_FLOATS floats) of the convolution that reads act(y), in ONE launch: the kernel splits the
+ * 16 bytes a lane is about to store.  y, hi, lo and scale[0] have the bits of the two launches; so has what the record shows to its
+ * readers -- the fold of the newer complete array, its tag, the two assumed words, the redo counter (single pairs may differ: a workgroup
+ * here writes the pairs b, b + G, ... of a grid of G workgroups with its own maximum).  relu / slope: the activation in front of the split
+ * (0 none, 1 ReLU, 2 LeakyReLU); y itself stays unactivated.  flags: WC_NARROW_SPLIT_NO_REDO leaves out the gated second pass (a launch
+ * of its own on y, as behind wc_conv_split_hist_f32), WC_NARROW_SPLIT_NT stores y with the non-temporal hint.
+ * wc_conv_fwd_narrow_split_supported: the narrow forward's shapes whose grid has at most 512 workgroups (one pair of the record each at
+ * least); WC_ERR_SHAPE otherwise -- the caller then runs the two launches. */
+#define WC_NARROW_SPLIT_NO_REDO 2
+#define WC_NARROW_SPLIT_NT 4
+int    wc_conv_fwd_narrow_split_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize);
+int    wc_conv_fwd_narrow_split_f32(const float* x, const float* w, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
+                                    const float* bias /*nullable*/, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize,
+                                    int relu, float slope, float* y, void* hi, void* lo, float* scale, float* hist, int flags,
+                                    wc_stream_t stream);
+
+/* wc_conv_wrw_narrow64_f32 with gy read through a ReLU's backward: the sums are those of gy[p][o] * (mask[p][o] <= 0 ? 0 : 1), mask of
+ * gy's shape (torch's threshold_backward(gy, mask, 0) predicate: a NaN in mask lets the gradient through) -- dw and db have the bits of
+ * the plain entry on the masked copy for every finite gy, and that copy is never written. */
+int    wc_conv_wrw_narrow_masked_f32(const float* x, const float* gy, const float* mask, int64_t N, int64_t H, int64_t W, int Cin, int Cout,
+                                     int ksize, float* dw, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
+                                     float* db /*nullable*/, void* ws, size_t ws_bytes, wc_stream_t stream);
+
 /* wc_conv_wrw_f16x3 plus the bias gradient db[Cout] = column sums of gy, from the partial rows wc_conv_split_colsum_f32
  * left while gy was split (fixed summation order, no extra launch). */
 int wc_conv_wrw_bias_f16x3(const void* xhi, const void* xlo, const float* xscale, const void* ghi, const void* glo,

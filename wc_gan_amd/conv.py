@@ -1210,6 +1210,158 @@ class _CriticBlock(torch.autograd.Function):
         return dx, dw1, db1, dw2, db2, dws, dbs, None, None, None, None, None, None, None, None
 
 
+# ---- the critic's FIRST block: conv1 -> ReLU -> conv2 as one autograd node -----------------------------------------------------------------
+# discriminator.ResBlockDown with is_first: y = conv2(relu(conv1(x))) [pooled]; conv1 reads images (the narrow-input kernels), its output
+# h is the critic's largest tensor.  As separate nodes h was written, read back whole to be split for conv2, and in the backward conv2's
+# data gradient went through torch's threshold_backward (two reads, one write of that size) only for the narrow weight gradient to read
+# the copy once.  Here:
+#   PLANES  conv1's kernel writes conv2's planes from the registers that hold h (wc_conv_fwd_narrow_split_f32), where conv2's record can
+#           be used (_reader_record) and the grid fits the record (narrow_split_supported); else the two launches.
+#   MASK    when the image needs no gradient -- the critic's own updates -- the narrow weight gradient reads conv2's data gradient as it
+#           comes and h beside it (wc_conv_wrw_narrow_masked_f32); when it does, threshold_backward, MIOpen's data gradient and the plain
+#           entry run as before (the data gradient reads the masked copy anyway).
+# conv2's launches, sites, roles and records are those of _FastConv; the shortcut and the block's add stay with the caller: same bits.
+# FIRST_BLOCK = False: the separate nodes; the two flags below switch one part each (tests, tools/first_block_bench.py).  Independent of
+# FUSED_BLOCK / FUSED_FINISH, which concern the blocks behind this one.
+FIRST_BLOCK = True
+FIRST_BLOCK_PLANES = True
+FIRST_BLOCK_MASK = True
+FIRST_BLOCK_NT = False          # y = h leaves conv1's kernel as non-temporal stores (measured: DESIGN.md section 4.5)
+
+
+def narrow_shapes_supported(xshape, wshape):
+    """narrow_wrw_supported from the shapes alone: x NHWC, w (Cout, Cin, k, k)"""
+    if not NARROW_WRW or len(xshape) != 4 or len(wshape) != 4:
+        return False
+    k = wshape[2]
+    if wshape[3] != k or k not in (1, 3) or wshape[1] != xshape[3]:
+        return False
+    N, H, W, C = xshape
+    return bool(_lib.load().wc_conv_narrow64_supported(N, H, W, C, wshape[0], k))
+
+
+def narrow_split_supported(xshape, wshape):
+    """Does conv1's kernel take this narrow-input layer with the reader's planes as a second output?  Shapes only: the narrow layers
+    (narrow_shapes_supported) whose grid has at most 512 workgroups -- one pair of the reader's record each at least."""
+    if not narrow_shapes_supported(xshape, wshape):
+        return False
+    N, H, W, C = xshape
+    return bool(_lib.load().wc_conv_fwd_narrow_split_supported(N, H, W, C, wshape[0], wshape[2]))
+
+
+def first_block_route(xshape, w1shape, record):
+    """What _CriticFirstBlock's forward runs for conv1 and conv2's input planes: 'planes' (one launch) or 'two' (narrow_forward +
+    split_planes) -- from the switch, the shapes and conv2's record (_reader_record's answer) alone."""
+    return 'planes' if (FIRST_BLOCK_PLANES and record is not None and narrow_split_supported(xshape, w1shape)) else 'two'
+
+
+def narrow_forward_split(x, w, bias, record, relu=True, role='x'):
+    """narrow_forward(x, w, bias) and split_planes(y, relu, site, role) of the site that owns `record` (a seeded record: _reader_record) in
+    one launch: -> y, (hi, lo, scale).  Raises where narrow_split_supported says no."""
+    lib = _lib.load()
+    N, H, W, C = x.shape
+    O, k = w.shape[0], w.shape[2]
+    y = torch.empty((N, H, W, O), dtype=torch.float32, device=x.device)
+    both = torch.empty((2, N, H, W, O), dtype=torch.float16, device=x.device)
+    scale = torch.empty(1 + 512, dtype=torch.float32, device=x.device)        # (split_planes' layout: [scale | scratch])
+    xc = x if x.is_contiguous() else x.contiguous()
+    flags = (0 if _guarded(role) else 2) | (4 if FIRST_BLOCK_NT else 0)      # WC_NARROW_SPLIT_NO_REDO, WC_NARROW_SPLIT_NT
+    _lib.check(lib.wc_conv_fwd_narrow_split_f32(_ptr(xc), _ptr(w), w.stride(1), w.stride(0), w.stride(2), w.stride(3), _ptr(bias), N, H, W, C, O, k,
+                                                1 if relu else 0, 0.0, _ptr(y), _ptr(both[0]), _ptr(both[1]), _ptr(scale), _ptr(record[0]), flags,
+                                                _stream()), "wc_conv_fwd_narrow_split_f32")
+    return y, (both[0], both[1], scale)
+
+
+def narrow_gradients(x, gy, w, has_bias, mask=None):
+    """(dW in w's strides, db | None) of the 'same' convolution of an image-like NHWC x from its fp32 output gradient: the launches of
+    _NarrowInConv.backward.  mask: gy is read through the backward of a ReLU whose pre-activation was `mask` (gy's shape) -- the bits of
+    narrow_gradients(x, threshold_backward(gy, mask, 0), ...) without that tensor (wc_conv_wrw_narrow_masked_f32)."""
+    N, H, W, C = x.shape
+    O, k = w.shape[0], w.shape[2]
+    lib = _lib.load()
+    dw = torch.empty_strided(w.shape, w.stride(), dtype=torch.float32, device=w.device)
+    if _storage_extent(dw) != dw.numel():
+        raise ValueError("weight must be dense")
+    db = torch.empty(O, dtype=torch.float32, device=w.device) if has_bias else None
+    nb = lib.wc_conv_wrw_narrow64_workspace_bytes(N, H, W, C, O, k)
+    ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    xc = x if x.is_contiguous() else x.contiguous()
+    g = gy if gy.is_contiguous() else gy.contiguous()
+    if mask is None:
+        _lib.check(lib.wc_conv_wrw_narrow64_f32(_ptr(xc), _ptr(g), N, H, W, C, O, k, _ptr(dw), dw.stride(1), dw.stride(0), dw.stride(2),
+                                                dw.stride(3), _ptr(db), _ptr(ws), nb, _stream()), "wc_conv_wrw_narrow64_f32")
+        return dw, db
+    if not (mask.is_contiguous() and mask.shape == g.shape and mask.dtype == torch.float32):
+        raise ValueError("narrow_gradients: the mask is a dense fp32 tensor of the gradient's shape")
+    _lib.check(lib.wc_conv_wrw_narrow_masked_f32(_ptr(xc), _ptr(g), _ptr(mask), N, H, W, C, O, k, _ptr(dw), dw.stride(1), dw.stride(0),
+                                                 dw.stride(2), dw.stride(3), _ptr(db), _ptr(ws), nb, _stream()), "wc_conv_wrw_narrow_masked_f32")
+    return dw, db
+
+
+class _CriticFirstBlock(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, sites, plan):
+        conv1, conv2 = sites
+        need = ctx.needs_input_grad
+        need_h = need[0] or need[1] or need[2]
+        rec = _reader_record(conv2, 'x', x.device)
+        if first_block_route(tuple(x.shape), tuple(w1.shape), rec) == 'planes':
+            h, h_pl = narrow_forward_split(x, w1, b1, rec, relu=True, role='x')
+        else:
+            h = narrow_forward(x, w1, b1)
+            h_pl = split_planes(h, relu=True, site=conv2, role='x')
+        img2, bimg2 = _images(w2, plan, need_h, conv2)
+        y = run(h_pl, img2, plan.fwd[0], b2, nbytes=plan.fwd_ws)
+        ctx.save_for_backward(x, h, w1, w2, *h_pl)
+        ctx.sites, ctx.plan, ctx.bimg2 = sites, plan, bimg2
+        ctx.has_bias = (b1 is not None, b2 is not None)
+        # h leaves for whoever watches the block's second norm site (see _CriticBlock): no gradient, none made up for it
+        ctx.mark_non_differentiable(h)
+        ctx.set_materialize_grads(False)
+        return y, h
+
+    @staticmethod
+    def backward(ctx, g, _gh):
+        x, h, w1, w2 = ctx.saved_tensors[:4]
+        h_pl = ctx.saved_tensors[4:7]
+        conv1, conv2 = ctx.sites
+        plan = ctx.plan
+        need = ctx.needs_input_grad
+        need_h = need[0] or need[1] or need[2]
+        if g is None:
+            return (None,) * 7
+        g = g.contiguous()
+        dx = dw1 = db1 = None
+        # conv2: _FastConv.backward's launches; its data gradient stays unmasked
+        fused2 = ctx.has_bias[1] and need[4] and need[3] and _colsum_ok(g.shape[-1])
+        g2 = split_planes(g, colsum=fused2, site=conv2, role='g')
+        dh, dw2, db2 = _layer_gradients(g2, fused2, h_pl, w2, plan, ctx.bimg2, need_h, need[3])
+        if ctx.has_bias[1] and need[4] and not fused2:
+            db2 = g.sum((0, 1, 2))
+        if need_h:
+            k = w1.shape[2]
+            want1 = need[1] or (ctx.has_bias[0] and need[2])
+            if need[0] or not FIRST_BLOCK_MASK:
+                dh = torch.ops.aten.threshold_backward(dh, h, 0)
+                if need[0]:
+                    dx = torch.ops.aten.convolution_backward(dh.permute(0, 3, 1, 2), x.permute(0, 3, 1, 2), w1, None, [1, 1], [k // 2, k // 2],
+                                                             [1, 1], False, [0, 0], 1, [True, False, False])[0].permute(0, 2, 3, 1)
+                if want1:
+                    dw1, db1 = narrow_gradients(x, dh, w1, ctx.has_bias[0])
+            elif want1:
+                dw1, db1 = narrow_gradients(x, dh, w1, ctx.has_bias[0], mask=h)
+        return dx, dw1, db1, dw2, db2, None, None
+
+
+def critic_first_block(x, w1, b1, w2, b2, sites, plan):
+    """conv2(relu(conv1(x))) of the critic's first block (see above): x NHWC fp32 on the GPU with a handful of channels
+    (narrow_wrw_supported(x, w1)), sites = (conv1's layer, conv2's), plan = conv2's ('same' or 'down3') on conv1's output.
+    -> (y, h): conv2's output and detached conv1's output, the tensor the block's second norm site sees."""
+    if _storage_extent(w1) != w1.numel():
+        w1 = w1.contiguous()
+    return _CriticFirstBlock.apply(x, w1, b1, w2, b2, sites, plan)
+
+
 def critic_block(x, w1, b1, w2, b2, ws, bs, sites, plans, down, next_site=None, x_planes=None, backward_tails=False):
     """One critic block behind the first (see above): x NHWC fp32 on the GPU, the three weights as their layers hand them out (ws / bs
     None: identity shortcut), sites = the three layer objects (the shortcut's None with ws), plans from critic_block_plans.

@@ -1241,7 +1241,12 @@ struct NarrowWrwArgs {
     int64_t M; int64_t pix_per_wave;                 // (even)
 };
 
-__global__ __launch_bounds__(512, 1) void conv_wrw_narrow_kernel(NarrowWrwArgs a)
+// MASKED (the critic's first block, conv._CriticFirstBlock): gy is conv2's data gradient as it comes and `mask` conv1's output h -- the
+// ReLU between the two is applied to the 16 bytes a lane has just loaded (wc_relu_mask_apply: threshold_backward's predicate), so the
+// masked copy of the block's largest tensor is never written or read.  A masked-out product is (+-0) * x onto an accumulator that
+// started as +0: the sums keep the bits they have behind threshold_backward's +0 for every finite gy.  The plain kernel keeps its code.
+template <bool MASKED>
+__device__ __forceinline__ void conv_wrw_narrow_body(const NarrowWrwArgs& a, const float* __restrict__ mask)
 {
     extern __shared__ __attribute__((aligned(16))) float nw_part[];     // [8 waves][4 q][16 r][64 lanes]
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1265,10 +1270,13 @@ __global__ __launch_bounds__(512, 1) void conv_wrw_narrow_kernel(NarrowWrwArgs a
     int64_t p1 = p0 + a.pix_per_wave;
     if (p1 > a.M) p1 = a.M;
     // (Cout % 128 == 64: the last group's upper half has no channels -- those lanes read the group's first ones, nobody reads their results)
-    const float* gyc = a.gy + grp * 128 + (grp * 128 + 4 * i < a.Cout ? 4 * i : 0);
+    const int gyo = grp * 128 + (grp * 128 + 4 * i < a.Cout ? 4 * i : 0);
+    const float* gyc = a.gy + gyo;
+    const float* mkc = MASKED ? mask + gyo : nullptr;                   // (the mask at the offset of gy's 16 bytes: clamped and half-group lanes too)
     constexpr int U = 8;
     for (int64_t p = p0; p < p1; p += 2 * U) {
         float av[U]; f32x4 bv[U];
+        [[maybe_unused]] f32x4 mv[MASKED ? U : 1];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int64_t pp = p + 2 * u + k;
@@ -1281,11 +1289,14 @@ __global__ __launch_bounds__(512, 1) void conv_wrw_narrow_kernel(NarrowWrwArgs a
             const float xv = a.x[inb ? ((int64_t)(n * a.H + iy) * a.W + ix) * a.Cin + c : 0];
             av[u] = inb ? xv : ((ok && is_one) ? 1.f : 0.f);
             bv[u] = *reinterpret_cast<const f32x4*>(gyc + (int64_t)pc * a.Cout);
+            if (MASKED) mv[u] = *reinterpret_cast<const f32x4*>(mkc + (int64_t)pc * a.Cout);
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u)
+        for (int u = 0; u < U; ++u) {
+            if (MASKED) bv[u] = wc_relu_mask_apply(bv[u], mv[u]);
 #pragma unroll
             for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u][q], acc[q], 0, 0, 0);
+        }
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q)
@@ -1301,6 +1312,13 @@ __global__ __launch_bounds__(512, 1) void conv_wrw_narrow_kernel(NarrowWrwArgs a
         for (int w = 1; w < 8; ++w) sum += nw_part[w * 4096 + e];
         out[e] = sum;
     }
+}
+
+__global__ __launch_bounds__(512, 1) void conv_wrw_narrow_kernel(NarrowWrwArgs a) { conv_wrw_narrow_body<false>(a, nullptr); }
+
+__global__ __launch_bounds__(512, 1) void conv_wrw_narrow_masked_kernel(NarrowWrwArgs a, const float* __restrict__ mask)
+{
+    conv_wrw_narrow_body<true>(a, mask);
 }
 
 // element e = (q, r, lane) of a partial -> row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), output channel 128 grp + 4 (lane & 31) + q.
@@ -1355,8 +1373,19 @@ struct NarrowFwdArgs {
 
 constexpr int kNarrowLd = 32 * 2 + 4;     // floats per pixel row of a wave's LDS tile (16-byte aligned, the two lane halves 16 banks apart)
 constexpr int kNarrowNQ = 2;          // 32-channel output blocks per wave: 64 channels (4 blocks took 316 registers: one wave per SIMD, 35 us)
-template <int KS>
-__global__ __launch_bounds__(256, 2) void conv_fwd_narrow_kernel(NarrowFwdArgs a)
+// SPLIT (the critic's first block, conv._CriticFirstBlock): the float4 a lane stores to y is the unit conv_split_elem works on, so the
+// kernel also leaves the planes of act(y) for the convolution that reads y next, scaled by that reader's record -- what
+// conv_split_hist_kernel would have left after reading all of y back.  The record has kAmaxBlocks pairs and this grid G <= kAmaxBlocks
+// workgroups (the host refuses more): workgroup b writes the pairs b, b + G, b + 2 G, ... with its maximum and the new tag -- a maximum
+// may be repeated, so the array is complete, its fold is the tensor's maximum, and a mixture of tags mid-launch is never complete: the
+// protocol's argument holds as it stands (no atomics, fences or counters).  nt: y leaves as non-temporal stores.
+struct NarrowSplitArgs {
+    _Float16* hi; _Float16* lo; float* scale_out; float* hist;
+    int act; float slope; int nt;                    // split_act's convention
+};
+
+template <int KS, bool SPLIT>
+__device__ __forceinline__ void conv_fwd_narrow_body(const NarrowFwdArgs& a, const NarrowSplitArgs* sp)
 {
     __shared__ __attribute__((aligned(16))) float nf_tile[4 * 32 * kNarrowLd];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1412,6 +1441,10 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_narrow_kernel(NarrowFwdArgs a
             av[s] = inb ? xv : (kind == 1 ? 1.f : 0.f);
         }
     };
+    [[maybe_unused]] HistPick pk = {0, 0, 1.0f};
+    [[maybe_unused]] float amax = 0.f;
+    [[maybe_unused]] const unsigned bid = blockIdx.y * gridDim.x + blockIdx.x;
+    if constexpr (SPLIT) pk = conv_hist_pick(sp->hist, sp->scale_out, bid);
     float av[KS], an[KS];
     if (t0 < t1) gather(t0, av);
     for (int t = t0; t < t1; ++t) {
@@ -1444,12 +1477,38 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_narrow_kernel(NarrowFwdArgs a
             const int row = 4 * j + (lane >> 4);
             const int64_t pr = (int64_t)t * 32 + row;
             const f32x4 v = *reinterpret_cast<const f32x4*>(tl + row * kNarrowLd + 4 * (lane & 15));
-            if (pr < a.M) *reinterpret_cast<f32x4*>(a.y + pr * a.Cout + grp * (32 * kNarrowNQ) + 4 * (lane & 15)) = v;
+            if constexpr (!SPLIT) {
+                if (pr < a.M) *reinterpret_cast<f32x4*>(a.y + pr * a.Cout + grp * (32 * kNarrowNQ) + 4 * (lane & 15)) = v;
+            } else if (pr < a.M) {                  // (a row past the tensor: no stores, no part in the maximum)
+                const int64_t e = pr * a.Cout + grp * (32 * kNarrowNQ) + 4 * (lane & 15);
+                if (sp->nt) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(a.y + e));
+                else *reinterpret_cast<f32x4*>(a.y + e) = v;
+                amax = conv_split_elem(split_act(v, sp->act, sp->slope), amax, pk.s, sp->hi, sp->lo, e >> 2);
+            }
         }
 #pragma unroll
         for (int s = 0; s < KS; ++s) av[s] = an[s];
     }
+    if constexpr (SPLIT) {
+        // publish (conv_hist_publish's fold and 8-byte store): the workgroup's pairs of the OTHER array
+        typedef float f32x2h __attribute__((ext_vector_type(2)));
+        __shared__ float nf_red[4];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+        if (lane == 0) nf_red[wave] = amax;
+        __syncthreads();
+        const f32x2h p = {fmaxf(fmaxf(nf_red[0], nf_red[1]), fmaxf(nf_red[2], nf_red[3])), __builtin_bit_cast(float, pk.tag)};
+        const unsigned G = gridDim.x * gridDim.y;
+        for (unsigned pair = bid + tid * G; pair < (unsigned)kAmaxBlocks; pair += 256u * G)
+            *reinterpret_cast<f32x2h*>(sp->hist + (1 - pk.src) * kHistArray + 2 * pair) = p;
+    }
 }
+
+template <int KS>
+__global__ __launch_bounds__(256, 2) void conv_fwd_narrow_kernel(NarrowFwdArgs a) { conv_fwd_narrow_body<KS, false>(a, nullptr); }
+
+template <int KS>
+__global__ __launch_bounds__(256, 2) void conv_fwd_narrow_split_kernel(NarrowFwdArgs a, NarrowSplitArgs s) { conv_fwd_narrow_body<KS, true>(a, &s); }
 
 void magic_u31(unsigned d, unsigned* mag, unsigned* sh)
 {
@@ -1979,13 +2038,10 @@ static int wrw_splits(const wc_conv_geom* g, int* tile)
 int wc_conv_wrw_narrow_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize);
 int wc_conv_narrow64_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize);
 
-int wc_conv_fwd_narrow_f32(const float* x, const float* w, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
-                           const float* bias, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize, int relu, float* y, wc_stream_t stream)
+// the argument block and grid of the narrow forward (both entries below: one source for the tiling)
+static dim3 narrow_fwd_args(NarrowFwdArgs& a, const float* x, const float* w, int64_t stride_k, int64_t stride_n, int64_t stride_r,
+                            int64_t stride_s, const float* bias, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize, int relu, float* y)
 {
-    if (!x || !w || !y) return WC_ERR_ARG;
-    if (!wc_conv_narrow64_supported(N, H, W, Cin, Cout, ksize) || N * H * W * Cin >= ((int64_t)1 << 31)) return WC_ERR_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    NarrowFwdArgs a = {};
     a.x = x; a.w = w; a.bias = bias; a.y = y;
     a.N = (int)N; a.H = (int)H; a.W = (int)W; a.Cin = Cin; a.Cout = Cout; a.ks = ksize; a.nrow = ksize * ksize * Cin; a.relu = relu;
     a.sk = stride_k; a.sn = stride_n; a.sr = stride_r; a.ss = stride_s;
@@ -2001,13 +2057,58 @@ int wc_conv_fwd_narrow_f32(const float* x, const float* w, int64_t stride_k, int
     a.tiles_per_wave = (a.ntiles + 1023) / 1024;           // x Cout / 64 workgroup columns: ~2 waves per SIMD at Cout = 128 (three, at 166 registers: 32.8 against 30.7 us)
     if (a.tiles_per_wave < 1) a.tiles_per_wave = 1;
     const int nwg = (a.ntiles + 4 * a.tiles_per_wave - 1) / (4 * a.tiles_per_wave);
+    return dim3(nwg, Cout / (32 * kNarrowNQ));
+}
+
+int wc_conv_fwd_narrow_f32(const float* x, const float* w, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
+                           const float* bias, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize, int relu, float* y, wc_stream_t stream)
+{
+    if (!x || !w || !y) return WC_ERR_ARG;
+    if (!wc_conv_narrow64_supported(N, H, W, Cin, Cout, ksize) || N * H * W * Cin >= ((int64_t)1 << 31)) return WC_ERR_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    NarrowFwdArgs a = {};
+    const dim3 grid = narrow_fwd_args(a, x, w, stride_k, stride_n, stride_r, stride_s, bias, N, H, W, Cin, Cout, ksize, relu, y);
     const int ks2 = (a.nrow + 2) / 2;                      // k-steps: the taps' rows + the bias row, in pairs
-    dim3 grid(nwg, Cout / (32 * kNarrowNQ));
     if (ks2 <= 2) hipLaunchKernelGGL(conv_fwd_narrow_kernel<2>, grid, dim3(256), 0, st, a);
     else if (ks2 <= 5) hipLaunchKernelGGL(conv_fwd_narrow_kernel<5>, grid, dim3(256), 0, st, a);
     else if (ks2 <= 10) hipLaunchKernelGGL(conv_fwd_narrow_kernel<10>, grid, dim3(256), 0, st, a);
     else if (ks2 <= 14) hipLaunchKernelGGL(conv_fwd_narrow_kernel<14>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(conv_fwd_narrow_kernel<16>, grid, dim3(256), 0, st, a);
+    return (int)hipGetLastError();
+}
+
+// every workgroup of the split variant owns at least one pair of the reader's record: a grid of at most kAmaxBlocks workgroups
+int wc_conv_fwd_narrow_split_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize)
+{
+    if (!wc_conv_narrow64_supported(N, H, W, Cin, Cout, ksize) || N * H * W * Cin >= ((int64_t)1 << 31)) return 0;
+    NarrowFwdArgs a = {};
+    const dim3 grid = narrow_fwd_args(a, nullptr, nullptr, 0, 0, 0, 0, nullptr, N, H, W, Cin, Cout, ksize, 0, nullptr);
+    return (int64_t)grid.x * grid.y <= kAmaxBlocks ? 1 : 0;
+}
+
+int wc_conv_fwd_narrow_split_f32(const float* x, const float* w, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
+                                 const float* bias, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize, int relu, float slope,
+                                 float* y, void* hi, void* lo, float* scale, float* hist, int flags, wc_stream_t stream)
+{
+    if (!x || !w || !y || !hi || !lo || !scale || !hist || relu < 0 || relu > 2 || (flags & ~(WC_NARROW_SPLIT_NO_REDO | WC_NARROW_SPLIT_NT)))
+        return WC_ERR_ARG;
+    if (!wc_conv_fwd_narrow_split_supported(N, H, W, Cin, Cout, ksize)) return WC_ERR_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    NarrowFwdArgs a = {};
+    const dim3 grid = narrow_fwd_args(a, x, w, stride_k, stride_n, stride_r, stride_s, bias, N, H, W, Cin, Cout, ksize, 0, y);
+    NarrowSplitArgs s = {(_Float16*)hi, (_Float16*)lo, scale, hist, relu, slope, (flags & WC_NARROW_SPLIT_NT) ? 1 : 0};
+    const int ks2 = (a.nrow + 2) / 2;
+    if (ks2 <= 2) hipLaunchKernelGGL(conv_fwd_narrow_split_kernel<2>, grid, dim3(256), 0, st, a, s);
+    else if (ks2 <= 5) hipLaunchKernelGGL(conv_fwd_narrow_split_kernel<5>, grid, dim3(256), 0, st, a, s);
+    else if (ks2 <= 10) hipLaunchKernelGGL(conv_fwd_narrow_split_kernel<10>, grid, dim3(256), 0, st, a, s);
+    else if (ks2 <= 14) hipLaunchKernelGGL(conv_fwd_narrow_split_kernel<14>, grid, dim3(256), 0, st, a, s);
+    else hipLaunchKernelGGL(conv_fwd_narrow_split_kernel<16>, grid, dim3(256), 0, st, a, s);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || (flags & WC_NARROW_SPLIT_NO_REDO)) return (int)e;
+    // the gated second pass: split_hist's launch behind its own, on y
+    const int64_t n4 = a.M * Cout / 4;
+    const unsigned g2 = grid_for(n4) < 64u ? grid_for(n4) : 64u;
+    hipLaunchKernelGGL(conv_split_redo_kernel, dim3(g2), dim3(256), 0, st, (const float*)y, n4, relu, (_Float16*)hi, (_Float16*)lo, scale, hist, slope);
     return (int)hipGetLastError();
 }
 
@@ -2045,9 +2146,10 @@ size_t wc_conv_wrw_narrow_workspace_bytes(int64_t N, int64_t H, int64_t W, int C
     return wc_conv_wrw_narrow_supported(N, H, W, Cin, Cout, ksize) ? wc_conv_wrw_narrow64_workspace_bytes(N, H, W, Cin, Cout, ksize) : 0;
 }
 
-int wc_conv_wrw_narrow64_f32(const float* x, const float* gy, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize,
-                             float* dw, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s, float* db,
-                             void* ws, size_t ws_bytes, wc_stream_t stream)
+// mask: nullptr = the plain kernel; else gy's shape, the ReLU's pre-activation applied as gy is read (conv_wrw_narrow_masked_kernel)
+static int wrw_narrow64(const float* x, const float* gy, const float* mask, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize,
+                        float* dw, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s, float* db,
+                        void* ws, size_t ws_bytes, wc_stream_t stream)
 {
     if (!x || !gy || !dw || !ws) return WC_ERR_ARG;
     if (!wc_conv_narrow64_supported(N, H, W, Cin, Cout, ksize)) return WC_ERR_SHAPE;
@@ -2062,12 +2164,29 @@ int wc_conv_wrw_narrow64_f32(const float* x, const float* gy, int64_t N, int64_t
     const int nparts = (int)narrow_wrw_parts(a.M, &a.pix_per_wave);
     const int ngrp = (Cout + 127) / 128;
     constexpr int lds = 8 * 4096 * 4;
-    hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(conv_wrw_narrow_kernel), lds);
+    hipError_t e = wc_set_max_lds(mask ? reinterpret_cast<const void*>(conv_wrw_narrow_masked_kernel)
+                                       : reinterpret_cast<const void*>(conv_wrw_narrow_kernel), lds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(conv_wrw_narrow_kernel, dim3(nparts, ngrp), dim3(512), lds, st, a);
+    if (mask) hipLaunchKernelGGL(conv_wrw_narrow_masked_kernel, dim3(nparts, ngrp), dim3(512), lds, st, a, mask);
+    else hipLaunchKernelGGL(conv_wrw_narrow_kernel, dim3(nparts, ngrp), dim3(512), lds, st, a);
     hipLaunchKernelGGL(conv_wrw_narrow_reduce_kernel, dim3(128, ngrp), dim3(256), 0, st, (const float*)ws, nparts, Cin, ksize, a.nrow,
                        dw, stride_k, stride_n, stride_r, stride_s, db, Cout);
     return (int)hipGetLastError();
+}
+
+int wc_conv_wrw_narrow64_f32(const float* x, const float* gy, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize,
+                             float* dw, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s, float* db,
+                             void* ws, size_t ws_bytes, wc_stream_t stream)
+{
+    return wrw_narrow64(x, gy, nullptr, N, H, W, Cin, Cout, ksize, dw, stride_k, stride_n, stride_r, stride_s, db, ws, ws_bytes, stream);
+}
+
+int wc_conv_wrw_narrow_masked_f32(const float* x, const float* gy, const float* mask, int64_t N, int64_t H, int64_t W, int Cin, int Cout,
+                                  int ksize, float* dw, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s, float* db,
+                                  void* ws, size_t ws_bytes, wc_stream_t stream)
+{
+    if (!mask) return WC_ERR_ARG;
+    return wrw_narrow64(x, gy, mask, N, H, W, Cin, Cout, ksize, dw, stride_k, stride_n, stride_r, stride_s, db, ws, ws_bytes, stream);
 }
 
 int wc_conv_wrw_narrow_f32(const float* x, const float* gy, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize,

@@ -12,6 +12,16 @@ __device__ __forceinline__ f32x4 wc_mask_apply(f32x4 v, const f32x4 p, float slo
     return v;
 }
 
+// The ReLU's backward on a gradient that feeds a SUM right away (the narrow weight gradient of the critic's first block, wc_conv.hip:
+// conv_wrw_narrow_body): torch's threshold_backward(v, p, 0) predicate, p <= 0 -- a NaN pre-activation lets the gradient THROUGH, unlike
+// wc_mask_apply's p > 0 -- as a multiply, so a masked-out element is (+-0) and leaves a sum that started as +0 as it would have been.
+__device__ __forceinline__ f32x4 wc_relu_mask_apply(f32x4 v, const f32x4 p)
+{
+    #pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = v[j] * (p[j] <= 0.f ? 0.f : 1.0f);
+    return v;
+}
+
 __device__ __forceinline__ f32x4 wc_colsum_add(f32x4 cs, f32x4 v)
 {
     #pragma unroll

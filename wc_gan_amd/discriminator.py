@@ -65,6 +65,40 @@ class ResBlockDown(nn.Module):
                                      tuple(self.shortcut.conv.weight.shape) if self.has_shortcut else None, self.resample == 'DOWN',
                                      ragged=fc._ragged(self.conv1))
 
+    def _first_plan(self, x):
+        """conv2's plan when the FIRST block's conv1 -> ReLU -> conv2 runs as one autograd node (conv.critic_first_block), else None: the
+        route switched on, no norm at the second site, conv1 a narrow-input layer on an image-like fp32 GPU tensor (the layer the
+        block kernels do not take), conv2 a 3x3 layer the block kernels take ('down3' in a DOWN block)."""
+        from . import generator as _g
+        # (any strides: the narrow kernels read a dense copy, as on the separate nodes -- the generator hands over a permuted view)
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+                and getattr(x, '_wc_planes', None) is None and _g.split_of(x) is None):
+            return None
+        return self._first_plan_of(tuple(x.shape))
+
+    def _first_plan_of(self, xshape):
+        """_first_plan's answer for a dense fp32 GPU tensor of this NHWC shape (the layers and the shapes alone)"""
+        from . import conv as fc, generator as _g
+        if not (self.is_first and fc.FIRST_BLOCK and _g.FAST_CONV):
+            return None
+        bn = self.bn2
+        if not (isinstance(bn, _g._UnfusedStack) and bn.norm_layer is None and len(bn.branches) == 0):
+            return None
+        if not all(isinstance(c, Conv2D) and c.kind == 'same' and c.conv.weight.dtype == torch.float32 for c in (self.conv1, self.conv2)):
+            return None
+        w1, w2 = self.conv1.conv.weight, self.conv2.conv.weight
+        if len(xshape) != 4 or tuple(w2.shape[2:]) != (3, 3) or w1.shape[0] <= 4:
+            return None
+        xs = fc._Shape(xshape)
+        p1 = fc._plan('same', xs, w1, fc._ragged(self.conv1))
+        if (p1 and p1.ok) or not fc.narrow_shapes_supported(xshape, tuple(w1.shape)):       # (a layer the block kernels take is not conv1 on images)
+            return None
+        if self.resample == 'DOWN' and (xshape[1] % 2 or xshape[2] % 2):
+            return None
+        hs = fc._Shape(tuple(xshape[:3]) + (w1.shape[0],))
+        p = fc._plan('down3' if self.resample == 'DOWN' else 'same', hs, w2, fc._ragged(self.conv2))
+        return p if (p and p.ok) else None
+
     def takes_input_planes(self, xshape):
         """Would this block, given a dense fp32 GPU tensor of this NHWC shape that the block in front has just written, run as the fused
         node -- so that the block in front may split it for conv1 (conv.critic_block's next_site) and hand the planes over?"""
@@ -97,6 +131,17 @@ class ResBlockDown(nn.Module):
             return y
         if x_planes is not None:
             raise RuntimeError("ResBlockDown: planes handed to a block that does not run as the fused node")
+        plan2 = self._first_plan(x)
+        if plan2 is not None:
+            # the first block's conv1 -> ReLU -> conv2 as one node (conv.critic_first_block); the shortcut and the add stay below
+            from . import conv as fc
+            h2, h = fc.critic_first_block(x, self.conv1._weight(), self.conv1.conv.bias, self.conv2._weight(), self.conv2.conv.bias,
+                                          (self.conv1, self.conv2), plan2)
+            self.bn2(h, cls)            # the identity (_first_plan checked): called so that a forward hook on the site sees its tensor
+            s = downsample2x(x) if self.resample == 'DOWN' else x
+            if self.has_shortcut:
+                s = self.shortcut(s)
+            return h2 + s
         # relu -> conv as one layer call: on the fast path the ReLU happens while the activation is split
         h = self.conv1(x) if self.is_first else self.conv1.forward_relu(self.bn1(x, cls))
         h = self.bn2(h, cls)
