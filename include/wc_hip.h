@@ -716,7 +716,8 @@ int    wc_conv_wrw_narrow_f32(const float* x, const float* gy, int64_t N, int64_
 
 /* The same three for Cout a multiple of 64 (the DC critic's first layer, 3 -> 64 at 3x3): a superset -- the entries above keep refusing
  * what they refused (callers size and gate by them).  A last group of 64 channels runs the 128-channel group with half its lanes idle;
- * the workspace holds one partial per STARTED 128 channels. */
+ * the workspace holds one partial per STARTED 128 channels.  Every narrow predicate and workspace function declines W < 2 (as the block
+ * convolutions do: the kernels' multiply-shift division of the pixel index wants divisors >= 2) -- such a layer is the caller's. */
 int    wc_conv_narrow64_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize);
 size_t wc_conv_wrw_narrow64_workspace_bytes(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize);
 int    wc_conv_wrw_narrow64_f32(const float* x, const float* gy, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize,

@@ -98,9 +98,9 @@ def _check_call(C, k, got, want, mine, twin):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # entry 1: the narrow forward that writes the reader's planes
 # ---------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.gpu
-@pytest.mark.parametrize("shape,cout,ks", CASES, ids=lambda v: 'x'.join(map(str, v)) if isinstance(v, tuple) else str(v))
-def test_narrow_forward_leaves_y_and_the_readers_planes_scale_and_record(shape, cout, ks):
+def _check_split_forward(shape, cout, ks):
+    """y, the reader's planes, the scale and the record of wc_conv_fwd_narrow_split_f32 against the two launches over a sequence of calls
+    (tests/test_narrow_edges_gpu.py runs it at its rows too)"""
     from wc_gan_amd import conv as C
     w, b = _layer(shape[-1], cout, ks)
     assert C.narrow_split_supported(shape, tuple(w.shape))
@@ -119,8 +119,10 @@ def test_narrow_forward_leaves_y_and_the_readers_planes_scale_and_record(shape, 
             want = _two_launches(C, x, w, bias, twin)
             obs = _check_call(C, k, got, want, mine, twin)
             assert obs[4] == (0 if k == 1 else 1), (k, 'redo')          # the gate fires once: at the 1000-fold call
-            if k == 2:      # ... and its result has the bits of the measured form
-                meas = C.split_planes(want[0], relu=True)
+            if k == 2:      # ... and its result has the bits of the measured form -- of the ACTIVATED tensor: the record holds max relu(y),
+                # conv_absmax_kernel measures max |y|, and where the largest |y| is a negative one a binade above (2x5x7, 2 -> 64, k = 1)
+                # the measured form of y itself takes half the scale
+                meas = C.split_planes(torch.relu(want[0]), relu=True)
                 for a, e, name in zip(got[1], meas, ('hi', 'lo', 'scale')):
                     assert _same_bits(a[:1] if name == 'scale' else a, e[:1] if name == 'scale' else e), (k, 'measured', name)
             if k == 3:
@@ -133,6 +135,12 @@ def test_narrow_forward_leaves_y_and_the_readers_planes_scale_and_record(shape, 
             _check_call(C, 5, got, _two_launches(C, x, w, b, twin), mine, twin)
         finally:
             C.FIRST_BLOCK_NT = old
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape,cout,ks", CASES, ids=lambda v: 'x'.join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_narrow_forward_leaves_y_and_the_readers_planes_scale_and_record(shape, cout, ks):
+    _check_split_forward(shape, cout, ks)
 
 
 @pytest.mark.gpu
@@ -206,12 +214,18 @@ def test_masked_narrow_weight_gradient_has_the_bits_of_the_masked_copy(shape, co
     """M = 50 with Cout = 64: clamped loads and the idle upper half of the 128-channel group.  The comparison is of the results' bits, not
     of the intermediate zeros: a masked-out element is g * 0 = (+-0) here and +0 in threshold_backward's copy (tests/test_critic_glue_gpu.py
     explains), which no sum that started as +0 can tell apart.  A NaN pre-activation lets the gradient through, as threshold_backward does."""
-    from wc_gan_amd import conv as C
     w, _ = _layer(shape[-1], cout, ks)
     x = _randn(shape, 31).cuda()
     gshape = shape[:3] + (cout,)
     g = (_randn(gshape, 32) * 0.8).cuda()
     h = _mask_tensor(gshape, 33).cuda()
+    _check_masked_gradient(x, g, h, w)
+
+
+def _check_masked_gradient(x, g, h, w):
+    """the masked weight gradient has the bits of narrow_gradients on threshold_backward's output (tests/test_narrow_edges_gpu.py runs it
+    at its rows too)"""
+    from wc_gan_amd import conv as C
     assert bool(torch.isnan(h).any()) and bool((h < 0).any()) and bool(torch.isfinite(g).all())
     want_dw, want_db = C.narrow_gradients(x, torch.ops.aten.threshold_backward(g, h, 0), w, True)
     got_dw, got_db = C.narrow_gradients(x, g, w, True, mask=h)

@@ -2125,6 +2125,7 @@ int wc_conv_narrow64_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cou
 {
     if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3)) return 0;
     if (ksize * ksize * Cin >= 32 || (Cout & 63)) return 0;
+    if (W < 2) return 0;                             // the multiply-shift division wants divisors >= 2 (conv_geom_ok's line)
     return N * H * W < ((int64_t)1 << 31) ? 1 : 0;
 }
 
