@@ -569,6 +569,15 @@ int wc_conv_supported(const wc_conv_geom* g);
  * has not opted in asks (wc_gan_amd/conv.py: a layer built with ragged_conv=True asks this one). */
 int wc_conv_ragged_supported(const wc_conv_geom* g);
 
+/* 1 when the geometry is one wc_conv_supported takes, or differs from one only in its output width: Cout any multiple of 32 (Cin as ever).
+ * N*H*W is a multiple of 128 -- whole tiles; a width that is 32 beyond a multiple of 64 on a partial last tile is in no set.  The launch
+ * entries wc_conv_f16x3 and wc_conv_wrw_[bias_]f16x3 (and the two *_workspace_bytes) accept the union of this set and
+ * wc_conv_ragged_supported's: Cout % 64 == 32 runs on 128-point x 32-output tiles, a weight gradient with Cin % 64 == 32 or
+ * Cout % 64 == 32 on 32 x 32 tiles, in either weight memory format.  wc_conv_res_supported / _tail_supported / _bwd_pair_supported answer
+ * 0 for a 32-wide side, and wc_conv_supported / wc_conv_ragged_supported keep their values: a caller that has not opted in asks those
+ * (wc_gan_amd/conv.py: a layer built with slim_conv=True asks this one). */
+int wc_conv_slim_supported(const wc_conv_geom* g);
+
 /* hi = fp16(s*x), lo = fp16(s*x - hi) over n floats (n % 4 == 0), s = the power of two that puts max|x| into
  * [2^13, 2^14) (written to *scale on the device); relu != 0 clamps at zero first.  `amax_scratch`: WC_CONV_SCRATCH_BYTES
  * device bytes (per-workgroup maxima; no atomics, nothing to clear). */

@@ -130,6 +130,7 @@ SIGNATURES = {
                                          c_void_p, c_size_t, c_void_p]),
     "wc_conv_supported": (c_int, [c_void_p]),
     "wc_conv_ragged_supported": (c_int, [c_void_p]),
+    "wc_conv_slim_supported": (c_int, [c_void_p]),
     "wc_conv_split_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wc_conv_weights_bytes": (c_size_t, [c_void_p]),
     "wc_conv_weights_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,

@@ -11,7 +11,8 @@
 Forward and the data gradient run on the HIP kernel (the data gradient of 'same' is a 'same', of 'down' an 'up' and of
 'up' a 'down', with the channel roles swapped in the weight image), and so does the weight gradient (pixel-major tiles
 read back through gfx950's transposing LDS read).  `relu_input` / `leaky_input` (fast_conv_or_none): the layer is conv(relu(x)) /
-conv(leaky_relu(x, slope)) and the activation happens while x is split.  Channel widths: multiples of 128, of 64 for 'down'.  N*H*W of the virtual grid (the output's
+conv(leaky_relu(x, slope)) and the activation happens while x is split.  Channel widths: multiples of 128, of 64 for 'down' -- of 32 for
+'same' and 'up3' in a layer built with slim_conv=True (`slim=` here).  N*H*W of the virtual grid (the output's
 for 'down' / 'down3', the input's otherwise): a multiple of 128, or -- for a layer built with ragged_conv=True (`ragged=` here) -- of 32:
 the last 128-point tile is then partial.  No fallback inside: `supported(...)` tells the caller whether the
 kernel takes a shape.
@@ -107,13 +108,19 @@ def _ragged(site):
     return bool(getattr(site, 'ragged_conv', False))
 
 
-def supported(x, w, kind, ragged=False):
+def _slim(site):
+    """Has the layer object opted in to the 64- and 32-channel tiles (make_generator(slim_conv=True))?"""
+    return bool(getattr(site, 'slim_conv', False))
+
+
+def supported(x, w, kind, ragged=False, slim=False):
     """Does the kernel take this call?  (channels multiples of 128 -- of 64 for kind 'down' --, N*H*W of the virtual grid a multiple of 128;
-    ragged, the opt-in of a layer marked ragged_conv: a multiple of 32, the last tile partial -- wc_conv_ragged_supported)"""
+    ragged, the opt-in of a layer marked ragged_conv: a multiple of 32, the last tile partial -- wc_conv_ragged_supported;
+    slim, the opt-in of a layer marked slim_conv: channels multiples of 32 on whole tiles -- wc_conv_slim_supported)"""
     handed = getattr(x, '_wc_planes', None) is not None       # a K3 handle: the data is in the planes it carries
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and (handed or x.is_contiguous()) and w.dtype == torch.float32):
         return False
-    p = _plan(kind, x, w, ragged)
+    p = _plan(kind, x, w, ragged, slim)
     return bool(p) and p.ok
 
 
@@ -122,7 +129,7 @@ class _Plan:
     support verdict and the workspace sizes (the per-call host work is what is left: a few allocations and launches)."""
     __slots__ = ('ok', 'fwd', 'bwd', 'fwd_ws', 'bwd_ws', 'wrw_ws', 'fwd_ptr', 'bwd_ptr', 'pair', 'res', 'tail', 'bwd_tail')
 
-    def __init__(self, kind, N, H, W, wshape, ragged=False):
+    def __init__(self, kind, N, H, W, wshape, ragged=False, slim=False):
         class _W:                                 # shape-only stand-in for the weight
             shape = wshape
         lib = _lib.load()
@@ -132,6 +139,10 @@ class _Plan:
         # ragged: the layer opted in to a partial last tile (N*H*W a multiple of 32); without it the answer is the one it always was
         takes = lib.wc_conv_ragged_supported if ragged else lib.wc_conv_supported
         self.ok = bool(takes(self.fwd_ptr)) and bool(takes(self.bwd_ptr))
+        # slim: the layer opted in to channel widths that are multiples of 32, on whole tiles.  A layer marked
+        # both ways is taken where either set takes both geometries: a slim width on a partial last tile is in neither
+        if slim and not self.ok:
+            self.ok = bool(lib.wc_conv_slim_supported(self.fwd_ptr)) and bool(lib.wc_conv_slim_supported(self.bwd_ptr))
         self.fwd_ws = lib.wc_conv_workspace_bytes(self.fwd_ptr) if self.ok else 0
         self.bwd_ws = lib.wc_conv_workspace_bytes(self.bwd_ptr) if self.ok else 0
         self.wrw_ws = lib.wc_conv_wrw_workspace_bytes(self.fwd_ptr) if self.ok else 0
@@ -147,8 +158,9 @@ class _Plan:
 _plans = {}
 
 
-def _plan(kind, x, w, ragged=False):
-    key = (kind, tuple(x.shape), tuple(w.shape), bool(ragged))
+def _plan(kind, x, w, ragged=False, slim=False):
+    # (an unmarked layer's key is the four-field one it always was; the slim mark adds a field)
+    key = (kind, tuple(x.shape), tuple(w.shape), bool(ragged)) + ((True,) if slim else ())
     p = _plans.get(key)
     if p is None:
         N, H, W, C = x.shape
@@ -162,9 +174,11 @@ def _plan(kind, x, w, ragged=False):
         # A width that is 64 beyond a multiple of 128 (the kernels' 64-wide tiles): the layer entry takes it for the plain 4x4 stride-2
         # convolution only -- the DC critic's 64 -> 128 layer.  The kernels take every geometry with such a width (_Plan.ok says so, and
         # tests/test_dcgan_conv_gpu.py runs them); the 64-wide ResNet blocks of toy configurations stay on their other path, as before.
-        if good and kind != 'down' and (C % 128 or w.shape[0] % 128 or w.shape[1] % 128):
+        # A layer marked slim_conv drops this rule for the generator's kinds: its 64-wide layers reach the kernels they always had, its
+        # 32-wide ones the 32-output and 32 x 32 tiles (wc_conv_slim_supported answers for both geometries).
+        if good and kind != 'down' and (C % 128 or w.shape[0] % 128 or w.shape[1] % 128) and not (slim and kind in ('same', 'up3')):
             good = False
-        p = _plans[key] = _Plan(kind, N, H, W, tuple(w.shape), bool(ragged)) if good else False
+        p = _plans[key] = _Plan(kind, N, H, W, tuple(w.shape), bool(ragged), bool(slim)) if good else False
     return p
 
 
@@ -848,15 +862,16 @@ def fast_conv_or_none(x, w, bias=None, kind='same', relu_input=False, site=None,
         raise ValueError("relu_input and leaky_input are two activations")
     handed = getattr(x, '_wc_planes', None)
     ragged = _ragged(site)                          # a layer marked ragged_conv takes a partial last tile (see supported)
-    if not supported(x, w, kind, ragged):
+    slim = _slim(site)                              # a layer marked slim_conv takes widths that are multiples of 32 (see supported)
+    if not supported(x, w, kind, ragged, slim):
         if handed is not None:
             raise _lib.WcHipError(f"fast_conv: a K3 handle reached a convolution that cannot take planes {tuple(x.shape)} x {tuple(w.shape)} ({kind})")
         return None
     if handed is not None:
         if relu_input or leaky_input is not None:
             raise ValueError("a K3 handle is already ReLU'd")
-        return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w, ragged), False, handed, site)
-    return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w, ragged), relu_input, None, site,
+        return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w, ragged, slim), False, handed, site)
+    return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w, ragged, slim), relu_input, None, site,
                            None if leaky_input is None else float(leaky_input))
 
 
@@ -985,16 +1000,16 @@ def narrow_out_wrw_supported(x, w):
     return bool(_lib.load().wc_conv_wrw_narrow_supported(N, H, W, w.shape[0], C, k))
 
 
-def fast_conv(x, w, bias=None, kind='same', residual=None, ragged=False):
+def fast_conv(x, w, bias=None, kind='same', residual=None, ragged=False, slim=False):
     """NHWC convolution (see the module docstring) -- raises if the shape is not one the kernel takes.
     residual: a tensor of the output's shape; the result is conv(x) + residual with the bits of that sum, added in the convolution's
     finish where the tap loop is shared over workgroups (wc_conv_res_f16x3), by an elementwise add behind the other geometries.
-    ragged: take a partial last tile (see supported)."""
-    if not supported(x, w, kind, ragged):
+    ragged: take a partial last tile; slim: take channel widths that are multiples of 32 (see supported)."""
+    if not supported(x, w, kind, ragged, slim):
         raise _lib.WcHipError(f"fast_conv: unsupported call {tuple(x.shape)} x {tuple(w.shape)} ({kind})")
     if residual is None:
-        return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w, ragged))
-    return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w, ragged), False, None, None, None, residual)
+        return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w, ragged, slim))
+    return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w, ragged, slim), False, None, None, None, residual)
 
 
 # ---- the critic's residual block as one autograd node ------------------------------------------------------------------------------------

@@ -20,6 +20,8 @@
 //     of k-step 0 right behind the barrier, then the MFMAs with the next iteration's addresses, DMAs and the fragment
 //     reads of k-step 1 in their shadow.
 //     NB = 1 (128 pixels x 64 outputs) is the tile of a width that is 64 beyond a multiple of 128 (the DC critic's 64-filter layers).
+//     A width that is 32 beyond a multiple of 64 (the ImageNet generator's 32-filter block): 128 pixels x 32 outputs, the four waves along
+//     the pixels (conv_f16x3_slim_kernel); its weight gradient on 32 x 32 tiles, a wave per pixel range (conv_wrw_slim_kernel).
 //   * small grids (< ~100 workgroups) share the (tap, chunk) loop over blockIdx.z (conv_ksplit_reduce_kernel finishes).
 //   * weight gradient: conv_wrw_kernel (pixel-major tiles, ds_read_b64_tr_b16 fragments, split over pixel ranges) +
 //     conv_wrw_reduce_kernel (fixed-order sum into the weight's layout, 4x4 slices folded back onto 3x3 taps); 256 x 256, 128 x 128 or
@@ -265,6 +267,133 @@ __global__ __launch_bounds__(256) void conv_f16x3_kernel(ConvArgs a) { conv_f16x
 // that the one above keeps its code
 template <int NB, bool KS>
 __global__ __launch_bounds__(256) void conv_f16x3_ragged_kernel(ConvArgs a) { conv_f16x3_body<2, NB, KS, true>(a, blockIdx.x, blockIdx.y, blockIdx.z); }
+
+// ---- 32-output tiles: a width that is 32 beyond a multiple of 64 (wc_conv_slim_supported; the ImageNet generator's 32-filter block) ----------
+// The body above lays its four waves out 2 x 2 and gives the second wave column the tile's outputs 32 NB ... 64 NB - 1: at 32 outputs that
+// column has nothing to own, and a masked 64-wide tile would gather, multiply and address twice what exists.  Here the tile is 128 points x
+// 32 outputs and the four waves lie ALONG THE POINTS: wave w owns the m-block m0 + 32 w (one 32 x 32 accumulator, 16 registers), stages its
+// own rows of A (four 1-KiB fragment images per iteration: 2 k-steps x hi | lo) and one of the four 1-KiB chunks of the single n-block's
+// weight fragments, which all four waves read.  The scheme is conv_f16x3_body's -- split operands, three MFMAs into one accumulator,
+// LDS-DMA gather with the zero line for padding, two stages, one barrier per (tap, 32-channel chunk) iteration, the next iteration's five
+// DMAs between this one's six MFMAs -- and so are the weight image's order (blockIdx.y = phase * (Cout / 32) + n-block), the epilogue's
+// row mapping and the k-split's partial sums: a lane's column is n-block * 32 + (lane & 31) < Cout, in y and in the partial sums alike.
+// Whole tiles only (N*H*W a multiple of 128): every row of every wave is a point of the grid.  LDS: 2 x (16 + 4) KiB.
+template <bool KS>
+__global__ __launch_bounds__(256) void conv_f16x3_slim_kernel(ConvArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int A_BYTES = 4 * 4 * 1024, B_BYTES = 4 * 1024, STAGE = A_BYTES + B_BYTES;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ntn = a.Cout >> 5;
+    const int phase = blockIdx.y / ntn, nt = blockIdx.y - phase * ntn;
+    const unsigned m0 = blockIdx.x * 128;
+    const unsigned HW = a.H * a.W;
+    const int koff = (lane >> 5) * 8;
+
+    int gy, gx;
+    unsigned gpix;                                  // input pixel index of (n, 0, 0)
+    {
+        const unsigned m = m0 + wave * 32 + (lane & 31);
+        const unsigned n = __umulhi(m, a.magHW) >> a.shHW, rem = m - n * HW;
+        const unsigned yy = __umulhi(rem, a.magW) >> a.shW, xx = rem - yy * a.W;
+        gy = yy * a.in_stride; gx = xx * a.in_stride; gpix = n * (a.Hin * a.Win);
+    }
+    const unsigned lds0 = (unsigned)(size_t)((__attribute__((address_space(3))) char*)smem);
+    const int nchunk = a.Cin >> 5;
+    const int iters = a.ntaps * nchunk;
+
+    f32x16 acc;
+    #pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+
+    const int it0 = KS ? (int)blockIdx.z * iters / a.ksplit : 0, it1 = KS ? ((int)blockIdx.z + 1) * iters / a.ksplit : iters;
+    int tabv = 0;                                   // lane t: packed (dy, dx) of tap t of this phase
+    if (lane < a.ntaps) tabv = (a.dy[phase][lane] & 0xff) | ((a.dx[phase][lane] & 0xff) << 8);
+    const char* pa[2];                              // next iteration: hi / lo source of this lane's A row (k-step 0)
+    int pstep = 0;                                  // bytes to k-step 1 (0 on the zero line)
+    const char* pw;                                 // next iteration: this wave's chunk of the weight fragments
+    unsigned sb_next = 0;
+    auto prep = [&](int it, int stage) {
+        const int tap = it / nchunk, ch = it - tap * nchunk;
+        const int p = __builtin_amdgcn_readlane(tabv, tap);
+        const int dy = (signed char)(p & 0xff), dx = (signed char)((p >> 8) & 0xff);
+        const int iy = gy + dy, ix = gx + dx;
+        const bool ok = (unsigned)iy < (unsigned)a.Hin && (unsigned)ix < (unsigned)a.Win;
+        const int64_t e = ((int64_t)(gpix + iy * a.Win + ix)) * a.Cin + ch * 32 + koff;
+        pa[0] = reinterpret_cast<const char*>(ok ? a.xhi + e : a.zero + koff);
+        pa[1] = reinterpret_cast<const char*>(ok ? a.xlo + e : a.zero + koff);
+        pstep = ok ? 32 : 0;
+        pw = a.wimg + ((((int64_t)(phase * a.ntaps + tap) * nchunk + ch) * ntn + nt) << 12) + wave * 1024 + lane * 16;
+        sb_next = __builtin_amdgcn_readfirstlane(lds0 + stage * STAGE);
+    };
+    auto dma = [&](int d) {
+        if (d < 4) {
+            const int ks = d >> 1, pl = d & 1;
+            lds_dma16(pa[pl] + ks * pstep, sb_next + ((wave * 2 + ks) * 2 + pl) * 1024);
+        } else {
+            lds_dma16(pw, sb_next + A_BYTES + wave * 1024);
+        }
+    };
+    f16x8 fa[2][2], fb[2][2];                       // [k-step][hi | lo]
+    auto frags = [&](int stage, int ks) {
+        const char* sa = smem + stage * STAGE + ((wave * 2 + ks) * 2) * 1024 + lane * 16;
+        const char* sb = smem + stage * STAGE + A_BYTES + (ks * 2) * 1024 + lane * 16;
+        fa[ks][0] = *reinterpret_cast<const f16x8*>(sa);
+        fa[ks][1] = *reinterpret_cast<const f16x8*>(sa + 1024);
+        fb[ks][0] = *reinterpret_cast<const f16x8*>(sb);
+        fb[ks][1] = *reinterpret_cast<const f16x8*>(sb + 1024);
+    };
+    prep(it0, 0);
+    #pragma unroll
+    for (int d = 0; d < 5; ++d) dma(d);
+    for (int it = it0; it < it1; ++it) {
+        const int stage = (it - it0) & 1;
+        __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0): this wave's chunks of the stage have landed
+        __syncthreads();                           // ... and everybody's; the other stage is free (its readers are done)
+        frags(stage, 0);
+        // the last iteration re-fetches its own data into the idle stage: no branch in the loop, nobody reads it
+        prep(it + 1 < it1 ? it + 1 : it, stage ^ 1);
+        __builtin_amdgcn_sched_barrier(0);
+        #pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            #pragma unroll
+            for (int prod = 0; prod < 3; ++prod) {
+                // lo*hi, hi*lo, hi*hi
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ks][prod == 0 ? 1 : 0], fb[ks][prod == 1 ? 1 : 0], acc, 0, 0, 0);
+                if (ks * 3 + prod < 5) {
+                    dma(ks * 3 + prod);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (ks == 0 && prod == 1) {
+                    frags(stage, 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);            // the idle stage's last DMAs
+    // epilogue: unscale, bias, scatter rows to their output pixels
+    const float inv = 1.0f / (a.xscale[0] * a.wscale[0]);
+    const int oy0 = a.offy[phase], ox0 = a.offx[phase];
+    const float bj = a.bias ? a.bias[nt * 32 + (lane & 31)] : 0.f;
+    #pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const unsigned row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const unsigned m = m0 + wave * 32 + row;
+        const unsigned n = __umulhi(m, a.magHW) >> a.shHW, rem = m - n * HW;
+        const unsigned yy = __umulhi(rem, a.magW) >> a.shW, xx = rem - yy * a.W;
+        const int64_t opix = ((int64_t)n * a.Hout + (yy * a.out_stride + oy0)) * a.Wout + (xx * a.out_stride + ox0);
+        const int64_t oe = opix * a.Cout + nt * 32 + (lane & 31);
+        if (KS) {                                   // raw partial sums; conv_ksplit_reduce_kernel finishes
+            a.partial[(int64_t)blockIdx.z * ((int64_t)a.N * a.Hout * a.Wout * a.Cout) + oe] = acc[r];
+        } else {
+            float v = acc[r] * inv + bj;
+            if (a.relu) v = fmaxf(v, 0.f);
+            a.y[oe] = v;
+        }
+    }
+}
 
 // ---- small grids: the (tap, chunk) loop split over blockIdx.z; y = (sum of the partial sums) / (sx*sw) + bias ---------
 struct KsplitReduceArgs {
@@ -1110,6 +1239,93 @@ __device__ __forceinline__ void conv_wrw_body(const WrwArgs& a, const unsigned b
 template <int MB, int NB>
 __global__ __launch_bounds__(256) void conv_wrw_kernel(WrwArgs a) { conv_wrw_body<MB, NB>(a, blockIdx.x, blockIdx.y); }
 
+// ---- 32 x 32 tiles: a side that is 32 beyond a multiple of 64 (wc_conv_slim_supported) --------------------------------------------------
+// One 32 x 32 result tile is one MFMA block: a single wave's work.  So the four waves of a workgroup do not share a tile's blocks, they
+// share its PIXELS: wave w of workgroup x is pixel range 4 x + w of the launch (`ranges` of them: wrw_prepare's split count), with two
+// LDS stages of its own (2 x 8 KiB a wave: the rows' and the columns' 16 pixels x 32 channels, k-step and hi | lo) that no other wave
+// reads or writes -- no workgroup barrier anywhere; a wave waits for its own LDS-DMAs (vmcnt) and the in-order issue of its transposing
+// reads and MFMAs keeps a stage's readers ahead of the DMAs that refill it.  The staging (pixel-major chunks), the ds_read_b64_tr_b16
+// fragments, the partial sums' layout [range][slice][rows][columns] and therefore conv_wrw_reduce_kernel are conv_wrw_body's; which
+// operand the 32-wide side is (rows or columns: x_cols in wrw_prepare) makes no difference here, both sides are cut into 32s.
+__global__ __launch_bounds__(256) void conv_wrw_slim_kernel(WrwArgs a, int ranges)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int STAGE = 8 * 1024;                 // A: [k-step][hi | lo] 1 KiB each, then B's four
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int rng = blockIdx.x * 4 + wave;
+    if (rng >= ranges) return;                      // (wave-uniform; the waves never meet at a barrier)
+    const int nta = a.A.C >> 5, ntb = a.B.C >> 5;
+    int idx = blockIdx.y;
+    const int tb = idx % ntb; idx /= ntb;
+    const int ta = idx % nta; idx /= nta;
+    const int tap = idx % a.ntaps, phase = idx / a.ntaps;
+    const int c0 = rng * a.cps, c1 = min(c0 + a.cps, a.nchunks);
+    const int dya = a.A.dy[phase][tap], dxa = a.A.dx[phase][tap], dyb = a.B.dy[phase][tap], dxb = a.B.dx[phase][tap];
+    const unsigned HW = a.H * a.W;
+    char* mine = smem + wave * (2 * STAGE);
+    const unsigned lds0 = (unsigned)(size_t)((__attribute__((address_space(3))) char*)mine);
+    const int c8 = (lane & 3) * 8;                  // this lane's 8 channels inside a 32-channel block
+
+    // the eight 1-KiB chunks of pixel chunk c -> stage
+    auto issue = [&](int c, int stage) {
+        const unsigned sbase = __builtin_amdgcn_readfirstlane(lds0 + stage * STAGE);
+        #pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const unsigned m = c * 32 + s * 16 + (lane >> 2);
+            const unsigned n = __umulhi(m, a.magHW) >> a.shHW, rem = m - n * HW;
+            const unsigned yy = __umulhi(rem, a.magW) >> a.shW, xx = rem - yy * a.W;
+            const int ay = yy * a.A.stride + dya, ax = xx * a.A.stride + dxa;
+            const int by = yy * a.B.stride + dyb, bx = xx * a.B.stride + dxb;
+            const bool oka = (unsigned)ay < (unsigned)a.A.Hp && (unsigned)ax < (unsigned)a.A.Wp;
+            const bool okb = (unsigned)by < (unsigned)a.B.Hp && (unsigned)bx < (unsigned)a.B.Wp;
+            const int64_t ea = ((int64_t)((n * a.A.Hp + ay) * a.A.Wp + ax)) * a.A.C + ta * 32 + c8;
+            const int64_t eb = ((int64_t)((n * a.B.Hp + by) * a.B.Wp + bx)) * a.B.C + tb * 32 + c8;
+            lds_dma16(oka ? a.A.hi + ea : a.zero + c8, sbase + (s * 2) * 1024);
+            lds_dma16(oka ? a.A.lo + ea : a.zero + c8, sbase + (s * 2 + 1) * 1024);
+            lds_dma16(okb ? a.B.hi + eb : a.zero + c8, sbase + 4096 + (s * 2) * 1024);
+            lds_dma16(okb ? a.B.lo + eb : a.zero + c8, sbase + 4096 + (s * 2 + 1) * 1024);
+        }
+    };
+
+    f32x16 acc;
+    #pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    // transposing-read address of this lane inside a 1-KiB (16 pixels x 64 B) block
+    const int tr_off = ((lane >> 5) * 8 + ((lane & 15) >> 2)) * 64 + (((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2;
+
+    if (c0 < c1) issue(c0, 0);
+    for (int c = c0; c < c1; ++c) {
+        const int stage = (c - c0) & 1;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the stage's chunks have landed (this wave's own; nobody else's are read)
+        const char* sa = mine + stage * STAGE;
+        f16x8 fa[2][2], fb[2][2];                   // [k-step][hi | lo]
+        #pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            fa[ks][0] = tr_read8(sa + (ks * 2) * 1024, tr_off);
+            fa[ks][1] = tr_read8(sa + (ks * 2 + 1) * 1024, tr_off);
+            fb[ks][0] = tr_read8(sa + 4096 + (ks * 2) * 1024, tr_off);
+            fb[ks][1] = tr_read8(sa + 4096 + (ks * 2 + 1) * 1024, tr_off);
+        }
+        // the other stage's readers are the chunk before's: an LDS queue answers in order, so with these fragments in, theirs are
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (c + 1 < c1) issue(c + 1, stage ^ 1);
+        #pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+            #pragma unroll
+            for (int prod = 0; prod < 3; ++prod)
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ks][prod == 0 ? 1 : 0], fb[ks][prod == 1 ? 1 : 0], acc, 0, 0, 0);
+    }
+
+    const int slice = phase * a.ntaps + tap, nslice = a.nphase * a.ntaps;
+    float* out = a.partial + ((int64_t)rng * nslice + slice) * a.A.C * a.B.C;
+    #pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int ci = ta * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        out[(int64_t)ci * a.B.C + tb * 32 + (lane & 31)] = acc[r];
+    }
+}
+
 struct WrwReduceArgs {
     const float* partial; int splits, nslice, Ca, Cb;    // partial [splits][slices][Ca][Cb]
     const float* xscale; const float* gscale;
@@ -1547,6 +1763,19 @@ hipError_t launch_conv(const ConvArgs& a, hipStream_t st)
     return hipGetLastError();
 }
 
+// the 128-point x 32-output tiles of a width that is 32 beyond a multiple of 64 (whole tiles: wc_conv_slim_supported)
+template <bool KS>
+hipError_t launch_conv_slim(const ConvArgs& a, hipStream_t st)
+{
+    constexpr int LDS = 2 * (4 * 4 * 1024 + 4 * 1024);
+    const int64_t M = (int64_t)a.N * a.H * a.W;
+    hipError_t e = wc_set_max_lds(reinterpret_cast<const void*>(conv_f16x3_slim_kernel<KS>), LDS);
+    if (e != hipSuccess) return e;
+    dim3 grid((unsigned)(M / 128), (unsigned)(a.nphase * (a.Cout / 32)), (unsigned)a.ksplit);
+    hipLaunchKernelGGL((conv_f16x3_slim_kernel<KS>), grid, dim3(256), LDS, st, a);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 extern "C" {
@@ -1808,11 +2037,11 @@ int wc_conv_absmax_batch_f32(const wc_conv_absmax_job* jobs, int count, wc_strea
 
 // rows: what N*H*W must be a multiple of -- 128 (whole tiles: wc_conv_supported) or 32 (whole m-blocks, a partial last tile:
 // wc_conv_ragged_supported); every other rule is shared
-static int conv_geom_ok(const wc_conv_geom* g, int rows)
+static int conv_geom_ok(const wc_conv_geom* g, int rows, int cout_mask = 63)
 {
     if (!g) return 0;
     if (g->ntaps < 1 || g->ntaps > kMaxTaps || g->nphase < 1 || g->nphase > kMaxPhase) return 0;
-    if ((g->Cin & 31) || (g->Cout & 63)) return 0;    // (Cout % 128 == 64: the 64-output tile <2, 1>)
+    if ((g->Cin & 31) || (g->Cout & cout_mask)) return 0;    // (Cout % 128 == 64: the 64-output tile <2, 1>; cout_mask 31: the slim set)
     const int64_t M = (int64_t)g->N * g->H * g->W;
     // (M <= 2^31 - 128: the last tile's rows past the grid stay below 2^31, where the multiply-shift division is exact)
     if (M <= 0 || (M % rows) || M > ((int64_t)1 << 31) - (rows == 128 ? 0 : 128)) return 0;
@@ -1828,6 +2057,15 @@ int wc_conv_supported(const wc_conv_geom* g) { return conv_geom_ok(g, 128); }
 // an unmarked layer (wc_gan_amd/conv.py) asks it.
 int wc_conv_ragged_supported(const wc_conv_geom* g) { return conv_geom_ok(g, 32); }
 
+// the third set the launch entries take: wc_conv_supported's rules with an output width that is any multiple of 32 -- a width 32 beyond a
+// multiple of 64 runs on tiles of 32 outputs (conv_f16x3_slim_kernel), a weight gradient with such a side on 32 x 32 tiles
+// (conv_wrw_slim_kernel).  Whole 128-point tiles only: a slim width on a partial last tile is in neither set.  The other two predicates
+// keep their values; a layer built with slim_conv=True asks this one (wc_gan_amd/conv.py).
+int wc_conv_slim_supported(const wc_conv_geom* g) { return conv_geom_ok(g, 128, 31); }
+
+// what wc_conv_f16x3 / wc_conv_workspace_bytes take: the union
+static int conv_takes(const wc_conv_geom* g) { return wc_conv_ragged_supported(g) || wc_conv_slim_supported(g); }
+
 static int64_t conv_tiles(int64_t M) { return (M + 127) / 128; }       // 128-point tiles along x, the last one partial or whole
 
 constexpr int kKsplitMaxWgs = 96;         // k-split only grids of at most this many output tiles ...
@@ -1839,7 +2077,8 @@ static int conv_ksplit(const wc_conv_geom* g)
     // small grids leave most CUs idle with 128-point x (128|256)-output tiles: share the (tap, chunk) loop
     const int64_t M = (int64_t)g->N * g->H * g->W;
     const bool wide = (g->Cout % 256) == 0;
-    const int64_t wgs = conv_tiles(M) * g->nphase * (g->Cout / (wide ? 256 : (g->Cout % 128) ? 64 : 128));
+    // (a width 32 beyond a multiple of 64: tiles of 32 outputs -- never a tile count of zero)
+    const int64_t wgs = conv_tiles(M) * g->nphase * (g->Cout / (wide ? 256 : (g->Cout % 64) ? 32 : (g->Cout % 128) ? 64 : 128));
     const int iters = g->ntaps * (g->Cin / 32);
     if (wgs > kKsplitMaxWgs || iters < 8) return 1;
     int k = (int)((kKsplitTargetWgs + wgs - 1) / wgs);
@@ -1849,7 +2088,7 @@ static int conv_ksplit(const wc_conv_geom* g)
 
 size_t wc_conv_workspace_bytes(const wc_conv_geom* g)
 {
-    if (!g) return 0;
+    if (!g || g->Cout < 32) return 0;
     const int k = conv_ksplit(g);
     return k > 1 ? (size_t)k * g->N * g->Hout * g->Wout * g->Cout * 4 : 0;
 }
@@ -1860,6 +2099,7 @@ static bool conv_big_tile(const wc_conv_geom* g, int ksplit)
     const int64_t M = (int64_t)g->N * g->H * g->W;
     const bool wide = (g->Cout % 256) == 0;
     const int64_t wgs_big = (M / 256) * g->nphase * (g->Cout / (wide ? 256 : 128));
+    if (g->Cout % 128) return false;                // (the 64- and 32-output tiles have no 256-point form)
     return ksplit == 1 && (M % 256) == 0 && wgs_big >= 256;
 }
 
@@ -1868,7 +2108,7 @@ static int conv_prepare(ConvArgs& a, const void* xhi, const void* xlo, const flo
                         const float* bias, const void* zero_line, const wc_conv_geom* g, int relu, float* y, void* ws, size_t ws_bytes)
 {
     if (!xhi || !xlo || !xscale || !wimage || !wscale || !zero_line || !g || !y) return WC_ERR_ARG;
-    if (!wc_conv_ragged_supported(g)) return WC_ERR_SHAPE;
+    if (!conv_takes(g)) return WC_ERR_SHAPE;
     a.xhi = (const _Float16*)xhi; a.xlo = (const _Float16*)xlo; a.zero = (const _Float16*)zero_line;
     a.wimg = (const char*)wimage; a.xscale = xscale; a.wscale = wscale; a.bias = bias; a.y = y;
     a.N = g->N; a.H = g->H; a.W = g->W; a.Hin = g->Hin; a.Win = g->Win; a.Cin = g->Cin; a.Cout = g->Cout;
@@ -1895,7 +2135,8 @@ int wc_conv_f16x3(const void* xhi, const void* xlo, const float* xscale, const v
     if (rc != WC_OK) return rc;
     const bool wide = (g->Cout % 256) == 0;
     hipError_t e;
-    if (g->Cout % 128)                                      e = a.ksplit > 1 ? launch_conv<2, 1, true>(a, st) : launch_conv<2, 1>(a, st);
+    if (g->Cout % 64)                                       e = a.ksplit > 1 ? launch_conv_slim<true>(a, st) : launch_conv_slim<false>(a, st);
+    else if (g->Cout % 128)                                 e = a.ksplit > 1 ? launch_conv<2, 1, true>(a, st) : launch_conv<2, 1>(a, st);
     else if (conv_big_tile(g, a.ksplit))                    e = wide ? launch_conv<4, 4>(a, st) : launch_conv<4, 2>(a, st);
     else if (a.ksplit > 1)                                  e = wide ? launch_conv<2, 4, true>(a, st) : launch_conv<2, 2, true>(a, st);
     else                                                    e = wide ? launch_conv<2, 4>(a, st) : launch_conv<2, 2>(a, st);
@@ -2023,8 +2264,18 @@ static int wrw_splits(const wc_conv_geom* g, int* tile)
     // 256 x 256 tiles when there are enough of them (a 1x1 convolution has one slice: 128 x 128 tiles then)
     const bool wide = (g->Cin % 256 == 0) && (g->Cout % 256 == 0) && g->nphase * g->ntaps * (g->Cin / 256) * (g->Cout / 256) >= 4;
     *tile = wide ? 256 : ((g->Cin % 128) || (g->Cout % 128)) ? 64 : 128;     // (a 64-channel side: 64 x 64 tiles)
+    if ((g->Cin % 64) || (g->Cout % 64)) *tile = 32;                          // (a 32-channel side: 32 x 32 tiles, conv_wrw_slim_kernel)
     const int tiles = g->nphase * g->ntaps * (g->Cin / *tile) * (g->Cout / *tile);
     const int64_t nchunks = (int64_t)g->N * g->H * g->W / 32;
+    if (*tile == 32) {
+        // a range is a WAVE here (four to a workgroup) and a partial sum is 4 KiB a slice: about 2048 waves over all tiles, in
+        // multiples of 32 ranges = 8 workgroups (the XCD argument below), at most 256
+        int64_t ranges = 2048 / (tiles < 1 ? 1 : tiles) / 32 * 32;
+        if (ranges < 32) ranges = 32;
+        if (ranges > 256) ranges = 256;
+        if (ranges > nchunks) ranges = nchunks;
+        return ranges < 1 ? 1 : (int)ranges;
+    }
     // The workgroups of one pixel range (one per slice and tile) read the same activations: a split count that is a
     // multiple of 8 puts them on one XCD (workgroup id mod 8), i.e. behind one L2 -- measured 650 against 790 us at
     // 128 x 32 x 32 x 256 x 256 for 56 against 28 ranges.  About two workgroups per CU in all.
@@ -2201,7 +2452,7 @@ int wc_conv_wrw_narrow_f32(const float* x, const float* gy, int64_t N, int64_t H
 
 size_t wc_conv_wrw_workspace_bytes(const wc_conv_geom* g)
 {
-    if (!g) return 0;
+    if (!g || g->Cin < 32 || g->Cout < 32) return 0;
     int tile;
     return (size_t)wrw_splits(g, &tile) * g->nphase * g->ntaps * g->Cin * g->Cout * 4;
 }
@@ -2222,7 +2473,8 @@ static int wrw_prepare(WrwPlan& p, const void* xhi, const void* xlo, const float
                        int64_t stride_r, int64_t stride_s, const float* colsum_partials, float* db, void* ws, size_t ws_bytes)
 {
     if (!xhi || !xlo || !xscale || !ghi || !glo || !gscale || !zero_line || !g || !dw || !ws) return WC_ERR_NULL;
-    if (!wc_conv_ragged_supported(g) || (g->Cin & 63) || g->W < 2 || g->H * g->W < 2) return WC_ERR_SHAPE;
+    // (the set it always took, or the slim set: any side a multiple of 32 on whole tiles)
+    if (!((wc_conv_ragged_supported(g) && !(g->Cin & 63)) || wc_conv_slim_supported(g)) || g->W < 2 || g->H * g->W < 2) return WC_ERR_SHAPE;
     if (ws_bytes < wc_conv_wrw_workspace_bytes(g)) return WC_ERR_WORKSPACE;
     if ((colsum_partials == nullptr) != (db == nullptr)) return WC_ERR_NULL;
     if (db && ((g->Cout & 3) || 256 % (g->Cout >> 2) != 0)) return WC_ERR_SHAPE;
@@ -2288,7 +2540,12 @@ int wc_conv_wrw_bias_f16x3(const void* xhi, const void* xlo, const float* xscale
     const int T = p.T;
     dim3 grid((unsigned)p.splits, (unsigned)p.tiles);
     hipError_t e = hipSuccess;
-    if (T == 256) {
+    if (T == 32) {
+        constexpr int LDS = 4 * 2 * 8 * 1024;       // four waves, two stages of 8 KiB each
+        e = wc_set_max_lds(reinterpret_cast<const void*>(conv_wrw_slim_kernel), LDS);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(conv_wrw_slim_kernel, dim3((unsigned)((p.splits + 3) / 4), (unsigned)p.tiles), dim3(256), LDS, st, a, p.splits);
+    } else if (T == 256) {
         constexpr int LDS = 2 * (2 * 4 * 4 * 1024 + 2 * 4 * 4 * 1024);
         e = wc_set_max_lds(reinterpret_cast<const void*>(conv_wrw_kernel<4, 4>), LDS);
         if (e != hipSuccess) return (int)e;

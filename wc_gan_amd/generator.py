@@ -106,11 +106,15 @@ class Conv2D(nn.Module):
     stride 2 (the DC critic's DOWN blocks): the 4x4 kernel only -- Keras 'same' then pads 1 and 1, torch's padding=1."""
 
     def __init__(self, in_channels, filters, kernel_size=(3, 3), use_bias=True, name=None, spectral=False,
-                 spectral_iterations=1, fully_diff_spectral=False, conv_singular=True, stride=1, ragged_conv=False):
+                 spectral_iterations=1, fully_diff_spectral=False, conv_singular=True, stride=1, ragged_conv=False, slim_conv=False):
         super().__init__()
         # ragged_conv (ours): the block kernels may take this layer at a grid whose N*H*W is a multiple of 32 but not of 128, on a partial
         # last tile (conv.supported(ragged=True), DESIGN.md section 4.21); off, the layer keeps the routes it always had
         self.ragged_conv = bool(ragged_conv)
+        # slim_conv (ours): the block kernels may take this layer at channel widths that are multiples of 32 or 64, not of 128 (the
+        # ImageNet generator's 64- and 32-filter blocks; conv.supported(slim=True), DESIGN.md section 4.22).  The planes hand-overs do
+        # not ask with the mark (takes_planes / takes_split): at these widths the site in front writes fp32 and the layer splits it
+        self.slim_conv = bool(slim_conv)
         k = kernel_size if isinstance(kernel_size, int) else kernel_size[0]
         if stride not in (1, 2) or (stride == 2 and k != 4):
             raise ValueError(f"Conv2D: stride 2 is built for the 4x4 kernel ('same' = padding 1), not {k}x{k} / {stride}")
@@ -519,14 +523,16 @@ def make_generator(input_noise_shape=(128,), output_channels=3, input_cls_shape=
                    block_norm='u', block_after_norm='cs', filters_emb=10,
                    last_norm='u', last_after_norm='cs', gan_type=None, arch='res',
                    spectral=False, fully_diff_spectral=False, spectral_iterations=1, conv_singular=True,
-                   process_group=None, fused_batch_norm=False, decomposition='cholesky', ragged_conv=False):
+                   process_group=None, fused_batch_norm=False, decomposition='cholesky', ragged_conv=False,
+                   slim_conv=False):
     """Same keyword surface as generator.py:93-98; returns an nn.Module called as G(z) or G(z, cls).
-    fused_batch_norm, decomposition: see create_norm.  ragged_conv (ours, default False): marks every convolution layer -- see Conv2D."""
+    fused_batch_norm, decomposition: see create_norm.  ragged_conv, slim_conv (ours, default False): mark every convolution layer -- see
+    Conv2D."""
     assert arch in ['res', 'dcgan']
     if spectral and (block_after_norm not in ('uconv', 'ucs', 'n') or last_after_norm not in ('uconv', 'ucs', 'n')):
         raise NotImplementedError("spectral-normalised conditional coloring (SNConditionalConv11/SNFactorizedConv11) "
                                   "is outside the WC hot path; no shipped recipe sets --generator_spectral")
-    conv_layer = partial(Conv2D, spectral=bool(spectral), ragged_conv=bool(ragged_conv))
+    conv_layer = partial(Conv2D, spectral=bool(spectral), ragged_conv=bool(ragged_conv), slim_conv=bool(slim_conv))
     mk = partial(create_norm, number_of_classes=number_of_classes, filters_emb=filters_emb, process_group=process_group,
                  fused_batch_norm=fused_batch_norm, decomposition=decomposition)
     block_norm_layer = mk(block_norm, block_after_norm)

@@ -605,6 +605,43 @@ MNIST_SCHEDULES = {
 }
 
 
+# profiles/imagenet_step.json (tools/imagenet_step.py: the captured G+D step at batch 64 with the generator's mark on against the same networks
+# with it off, 7 alternating rounds): the marked step is faster in every round
+IMAGENET_SLIM_SHIPS = True
+
+
+# scripts/imagenet_resnet_sn_cond_sa.sh with run.py:147-237 for --dataset imagenet.  Generator: --generator_filters 128 (script line 6), a
+# (4, 4, 128) first block (run.py:152-153), five UP blocks of F, F, F, F/2, F/4 filters (run.py:159-163), 1000 classes (run.py:172-173), norms
+# d / ufconv in the blocks and d / uconv at the last site (script lines 5-6), --filters_emb 32 (line 8), --gan_type PROJECTIVE (line 7).
+# Critic: --discriminator_filters 1024 (line 6), widths F/16, F/8, F/4, F/2, F, F (run.py:206-207), five DOWN blocks and a SAME one
+# (run.py:208), 128 x 128 x 3 images (run.py:334), spectral normalisation (line 7), --sum_pool 1 (run.py:310, its default), hinge objectives
+# (lines 4-5), batch 64 (line 8).  Its 128 -> 64 and 64 -> 32 generator blocks (64 x 64 and 128 x 128 pixels) run on the block kernels where
+# slim_conv is on.  --shred_disc_batch 1 (line 8) is NOT reproduced: it lives in the reference's gan/ runtime,
+# which is not part of the tree this project was built from.  NOT in CONFIGS (bench.py's names); the schedule in a table of its own.
+IMAGENET_CONFIGS = {'imagenet_cond_sa': dict(
+    generator=dict(block_sizes=(128, 128, 128, 64, 32), resamples=("UP", "UP", "UP", "UP", "UP"), first_block_shape=(4, 4, 128),
+                   number_of_classes=1000, block_norm='d', block_after_norm='ufconv', filters_emb=32, last_norm='d',
+                   last_after_norm='uconv', gan_type='PROJECTIVE', slim_conv=IMAGENET_SLIM_SHIPS),
+    discriminator=dict(input_image_shape=(128, 128, 3), block_sizes=(64, 128, 256, 512, 1024, 1024),
+                       resamples=('DOWN', 'DOWN', 'DOWN', 'DOWN', 'DOWN', 'SAME'), number_of_classes=1000, type='PROJECTIVE',
+                       spectral=True, sum_pool=True, conv_singular=False, filters_emb=32),
+    image_shape=(128, 128, 3), conditional=True)}
+IMAGENET_SCHEDULES = {
+    # scripts/imagenet_resnet_sn_cond_sa.sh:7 (linear, 450 epochs) and :8 (--generator_lr 5e-4 --discriminator_lr 5e-4)
+    'imagenet_cond_sa': dict(lr_decay_schedule='linear', number_of_epochs=450, generator_lr=5e-4, discriminator_lr=5e-4),
+}
+
+
+def slim_config(config, on=True):
+    """The same recipe with every convolution layer of the GENERATOR marked slim_conv (make_generator(slim_conv=True), DESIGN.md section
+    4.22): the block kernels then take its 64- and 32-channel layers.  The critic has no such mark (its 64-wide layers would enter the fused
+    critic nodes, which have never run at that width).  A copy of any entry, the entry itself is left alone; on=False: the mark off."""
+    import copy
+    out = copy.deepcopy(config)
+    out['generator'].update(slim_conv=bool(on))
+    return out
+
+
 # --lr_decay_schedule / --number_of_epochs of each recipe's script: GanTrainer's arguments of the same names (the config tables above carry
 # the networks alone and are left as they are).  build_trainer(CONFIGS[name], **RECIPE_SCHEDULES[name]) trains the recipe at its script's rates.
 RECIPE_SCHEDULES = {
