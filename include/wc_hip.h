@@ -771,6 +771,22 @@ int    wc_conv_wrw_narrow_masked_f32(const float* x, const float* gy, const floa
                                      int ksize, float* dw, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
                                      float* db /*nullable*/, void* ws, size_t ws_bytes, wc_stream_t stream);
 
+/* 'same' convolution (1x1 or 3x3, stride 1) with a handful of OUTPUT channels -- the data gradient of an image layer (the critic's first
+ * block: conv1 and the 1x1 shortcut, discriminator.py:41-54 on images).  g [N,H,W,Cw] fp32 NHWC is the wide tensor, out [N,H,W,Cn], p = ksize / 2:
+ *     out[n][y][x][c] = sum_{r,s} sum_o m(g)[n][y - (r - p)][x - (s - p)][o] * w[o*stride_k + c*stride_n + r*stride_r + s*stride_s]
+ * positions outside the image contributing zero.  m(g) = g, or with `mask` (nullable; g's shape) threshold_backward(g, mask, 0):
+ * g[..] * (mask[..] <= 0 ? 0 : 1), applied as g is read -- the masked copy is never written.  With w the layer's (Cw, Cn, k, k) weight,
+ * stride_k / stride_n = its strides 0 / 1, this is the layer's data gradient; with the tap strides negated (w pointing at its last
+ * tap) and the channel strides exchanged it is the forward of a layer (Cn, Cw, k, k) with few outputs.  One pass over g (and mask) on the
+ * fp32 matrix pipe, no atomics, a fixed summation order: the same bits on every call.  Additive: WC_ABI_VERSION keeps its value.
+ * wc_conv_narrow_out_supported: ksize in {1, 3}, ksize^2 * Cn < 32, Cw % 32 == 0, W >= 2, N*H*W < 2^31, and the weight with ksize image
+ * rows of the per-pixel products within a workgroup's LDS (80 KiB: W * (ksize^2 * Cn | 1) * ksize + 32 * Cw floats); WC_ERR_SHAPE
+ * otherwise, nothing launched.  g and mask 16-byte aligned (WC_ERR_ARG). */
+int    wc_conv_narrow_out_supported(int64_t N, int64_t H, int64_t W, int Cw, int Cn, int ksize);
+int    wc_conv_narrow_out_f32(const float* g, const float* mask /*nullable*/, const float* w, int64_t stride_k, int64_t stride_n,
+                              int64_t stride_r, int64_t stride_s, int64_t N, int64_t H, int64_t W, int Cw, int Cn, int ksize,
+                              float* out, wc_stream_t stream);
+
 /* wc_conv_wrw_f16x3 plus the bias gradient db[Cout] = column sums of gy, from the partial rows wc_conv_split_colsum_f32
  * left while gy was split (fixed summation order, no extra launch). */
 int wc_conv_wrw_bias_f16x3(const void* xhi, const void* xlo, const float* xscale, const void* ghi, const void* glo,

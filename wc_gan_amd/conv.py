@@ -12,7 +12,8 @@ Forward and the data gradient run on the HIP kernel (the data gradient of 'same'
 'up' a 'down', with the channel roles swapped in the weight image), and so does the weight gradient (pixel-major tiles
 read back through gfx950's transposing LDS read).  `relu_input` / `leaky_input` (fast_conv_or_none): the layer is conv(relu(x)) /
 conv(leaky_relu(x, slope)) and the activation happens while x is split.  Channel widths: multiples of 128, of 64 for 'down' -- of 32 for
-'same' and 'up3' in a layer built with slim_conv=True (`slim=` here).  N*H*W of the virtual grid (the output's
+'same' and 'up3' in a layer built with slim_conv=True (`slim=` here), of 64 for 'same' and 'down3' in a critic
+layer built with slim_blocks=True (`blocks=` here; section 4.23).  N*H*W of the virtual grid (the output's
 for 'down' / 'down3', the input's otherwise): a multiple of 128, or -- for a layer built with ragged_conv=True (`ragged=` here) -- of 32:
 the last 128-point tile is then partial.  No fallback inside: `supported(...)` tells the caller whether the
 kernel takes a shape.
@@ -113,14 +114,20 @@ def _slim(site):
     return bool(getattr(site, 'slim_conv', False))
 
 
-def supported(x, w, kind, ragged=False, slim=False):
+def _blocks(site):
+    """Has the layer object opted in to the critic's 64-wide block layers (make_discriminator(slim_blocks=True))?"""
+    return bool(getattr(site, 'slim_blocks', False))
+
+
+def supported(x, w, kind, ragged=False, slim=False, blocks=False):
     """Does the kernel take this call?  (channels multiples of 128 -- of 64 for kind 'down' --, N*H*W of the virtual grid a multiple of 128;
     ragged, the opt-in of a layer marked ragged_conv: a multiple of 32, the last tile partial -- wc_conv_ragged_supported;
-    slim, the opt-in of a layer marked slim_conv: channels multiples of 32 on whole tiles -- wc_conv_slim_supported)"""
+    slim, the opt-in of a layer marked slim_conv: channels multiples of 32 on whole tiles -- wc_conv_slim_supported;
+    blocks, the opt-in of a layer marked slim_blocks: the critic's kinds 'same' and 'down3' at widths that are multiples of 64)"""
     handed = getattr(x, '_wc_planes', None) is not None       # a K3 handle: the data is in the planes it carries
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and (handed or x.is_contiguous()) and w.dtype == torch.float32):
         return False
-    p = _plan(kind, x, w, ragged, slim)
+    p = _plan(kind, x, w, ragged, slim, blocks)
     return bool(p) and p.ok
 
 
@@ -158,9 +165,9 @@ class _Plan:
 _plans = {}
 
 
-def _plan(kind, x, w, ragged=False, slim=False):
-    # (an unmarked layer's key is the four-field one it always was; the slim mark adds a field)
-    key = (kind, tuple(x.shape), tuple(w.shape), bool(ragged)) + ((True,) if slim else ())
+def _plan(kind, x, w, ragged=False, slim=False, blocks=False):
+    # (an unmarked layer's key is the four-field one it always was; the slim mark adds a field, the slim_blocks mark a further one)
+    key = (kind, tuple(x.shape), tuple(w.shape), bool(ragged)) + ((True,) if slim else ()) + (('blocks',) if blocks else ())
     p = _plans.get(key)
     if p is None:
         N, H, W, C = x.shape
@@ -176,7 +183,11 @@ def _plan(kind, x, w, ragged=False, slim=False):
         # tests/test_dcgan_conv_gpu.py runs them); the 64-wide ResNet blocks of toy configurations stay on their other path, as before.
         # A layer marked slim_conv drops this rule for the generator's kinds: its 64-wide layers reach the kernels they always had, its
         # 32-wide ones the 32-output and 32 x 32 tiles (wc_conv_slim_supported answers for both geometries).
-        if good and kind != 'down' and (C % 128 or w.shape[0] % 128 or w.shape[1] % 128) and not (slim and kind in ('same', 'up3')):
+        # A layer marked slim_blocks (make_discriminator(slim_blocks=True)) drops it for the critic's kinds where
+        # every width is a multiple of 64: the verdict is wc_conv_supported's (wc_conv_ragged_supported's with ragged), as for any layer.
+        wide64 = not (C % 64 or w.shape[0] % 64 or w.shape[1] % 64)
+        if good and kind != 'down' and (C % 128 or w.shape[0] % 128 or w.shape[1] % 128) and not (slim and kind in ('same', 'up3')) \
+                and not (blocks and kind in ('same', 'down3') and wide64):
             good = False
         p = _plans[key] = _Plan(kind, N, H, W, tuple(w.shape), bool(ragged), bool(slim)) if good else False
     return p
@@ -863,15 +874,16 @@ def fast_conv_or_none(x, w, bias=None, kind='same', relu_input=False, site=None,
     handed = getattr(x, '_wc_planes', None)
     ragged = _ragged(site)                          # a layer marked ragged_conv takes a partial last tile (see supported)
     slim = _slim(site)                              # a layer marked slim_conv takes widths that are multiples of 32 (see supported)
-    if not supported(x, w, kind, ragged, slim):
+    blocks = _blocks(site)                          # a layer marked slim_blocks takes the critic's kinds at multiples of 64 (see supported)
+    if not supported(x, w, kind, ragged, slim, blocks):
         if handed is not None:
             raise _lib.WcHipError(f"fast_conv: a K3 handle reached a convolution that cannot take planes {tuple(x.shape)} x {tuple(w.shape)} ({kind})")
         return None
     if handed is not None:
         if relu_input or leaky_input is not None:
             raise ValueError("a K3 handle is already ReLU'd")
-        return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w, ragged, slim), False, handed, site)
-    return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w, ragged, slim), relu_input, None, site,
+        return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w, ragged, slim, blocks), False, handed, site)
+    return _FastConv.apply(x, w, bias, kind, _plan(kind, x, w, ragged, slim, blocks), relu_input, None, site,
                            None if leaky_input is None else float(leaky_input))
 
 
@@ -913,14 +925,66 @@ def narrow_forward(x, w, bias=None, relu=False, mirrored=False):
     return y
 
 
+# The data gradient of the critic's image layers (3x3 conv1 and the 1x1 shortcut of the first block; wanted in the generator's update only) was
+# MIOpen's, in front of it torch's threshold_backward over the critic's largest tensor.  A layer marked slim_blocks takes it on the fp32 matrix
+# pipe instead (wc_conv_narrow_out_f32), the ReLU's mask applied as the gradient is read.  NARROW_OUT = False: the
+# marked layers keep MIOpen's (tests and tools/imagenet_critic_step.py compare the two in one process); unmarked layers never ask.
+NARROW_OUT = True
+
+
+def narrow_out_supported(gshape, wshape, forward=False):
+    """Does wc_conv_narrow_out_f32 take a wide NHWC tensor of this shape with this weight?  Shapes only: w (Cw, Cn, k, k), the layer whose
+    data gradient is asked for -- (Cn, Cw, k, k) with forward=True, the layer with few outputs itself."""
+    if len(gshape) != 4 or len(wshape) != 4 or wshape[2] != wshape[3]:
+        return False
+    cw, cn = (wshape[1], wshape[0]) if forward else (wshape[0], wshape[1])
+    N, H, W, C = gshape
+    return C == cw and bool(_lib.load().wc_conv_narrow_out_supported(N, H, W, cw, cn, wshape[2]))
+
+
+def narrow_out_conv(g, w, mask=None, forward=False):
+    """wc_conv_narrow_out_f32: the 'same' convolution of the wide NHWC fp32 tensor g down to a handful of channels.  w (Cw, Cn, k, k), any
+    dense layout: the DATA GRADIENT of the layer w belongs to, g its output gradient.  forward=True: w is (Cn, Cw, k, k) and the result
+    that layer's output (its taps read back to front, the channel strides exchanged).  mask (g's shape): g is read through the backward
+    of a ReLU whose pre-activation was `mask` -- the values of threshold_backward(g, mask, 0), which is never written."""
+    N, H, W, C = g.shape
+    k = w.shape[2]
+    if _storage_extent(w) != w.numel():
+        raise ValueError("weight must be dense")
+    if forward:
+        cn = w.shape[0]
+        ptr = ctypes.c_void_p(w.data_ptr() + 4 * ((k - 1) * w.stride(2) + (k - 1) * w.stride(3)))
+        strides = (w.stride(1), w.stride(0), -w.stride(2), -w.stride(3))
+    else:
+        cn = w.shape[1]
+        ptr = _ptr(w)
+        strides = (w.stride(0), w.stride(1), w.stride(2), w.stride(3))
+    gc = g if g.is_contiguous() else g.contiguous()
+    if mask is not None:
+        if not (mask.shape == g.shape and mask.dtype == torch.float32):
+            raise ValueError("narrow_out_conv: the mask is an fp32 tensor of g's shape")
+        mask = mask if mask.is_contiguous() else mask.contiguous()
+    out = torch.empty((N, H, W, cn), dtype=torch.float32, device=g.device)
+    _lib.check(_lib.load().wc_conv_narrow_out_f32(_ptr(gc), _ptr(mask), ptr, *strides, N, H, W, C, cn, k, _ptr(out), _stream()),
+               "wc_conv_narrow_out_f32")
+    return out
+
+
+def _narrow_out_route(site, gshape, wshape):
+    """Does the data gradient of this image layer run on wc_conv_narrow_out_f32?  The layer marked slim_blocks, the switch on, the shape taken."""
+    return NARROW_OUT and _blocks(site) and narrow_out_supported(tuple(gshape), tuple(wshape))
+
+
 class _NarrowInConv(torch.autograd.Function):
     """'same' convolution of an image-like input (k*k*Cin < 32): forward and weight / bias gradient on the fp32 matrix pipe
-    (wc_conv_fwd_narrow_f32, wc_conv_wrw_narrow_f32); the data gradient -- wanted in the generator update only -- by MIOpen."""
+    (wc_conv_fwd_narrow_f32, wc_conv_wrw_narrow_f32); the data gradient -- wanted in the generator update only -- by MIOpen, or for a
+    layer marked slim_blocks (site) by wc_conv_narrow_out_f32."""
 
     @staticmethod
-    def forward(ctx, x, w, bias):
+    def forward(ctx, x, w, bias, site=None):
         ctx.save_for_backward(x, w)
         ctx.has_bias = bias is not None
+        ctx.site = site
         return narrow_forward(x, w, bias)
 
     @staticmethod
@@ -931,7 +995,9 @@ class _NarrowInConv(torch.autograd.Function):
         lib = _lib.load()
         dx = dw = db = None
         g = gy if gy.is_contiguous() else gy.contiguous()
-        if ctx.needs_input_grad[0]:
+        if ctx.needs_input_grad[0] and _narrow_out_route(ctx.site, g.shape, w.shape):
+            dx = narrow_out_conv(g, w)
+        elif ctx.needs_input_grad[0]:
             dx = torch.ops.aten.convolution_backward(g.permute(0, 3, 1, 2), x.permute(0, 3, 1, 2), w, None, [1, 1], [k // 2, k // 2], [1, 1],
                                                      False, [0, 0], 1, [True, False, False])[0].permute(0, 2, 3, 1)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
@@ -944,7 +1010,7 @@ class _NarrowInConv(torch.autograd.Function):
             xc = x if x.is_contiguous() else x.contiguous()
             _lib.check(lib.wc_conv_wrw_narrow64_f32(_ptr(xc), _ptr(g), N, H, W, C, O, k, _ptr(dw), dw.stride(1), dw.stride(0), dw.stride(2),
                                                     dw.stride(3), _ptr(db), _ptr(ws), nb, _stream()), "wc_conv_wrw_narrow64_f32")
-        return dx, dw, db
+        return dx, dw, db, None
 
 
 def narrow_weight_gradient(x, gy, w):
@@ -965,11 +1031,12 @@ def narrow_weight_gradient(x, gy, w):
     return dw
 
 
-def narrow_in_conv(x, w, bias=None):
-    """y = conv(x, w) + bias for NHWC x with a handful of channels (narrow_wrw_supported)"""
+def narrow_in_conv(x, w, bias=None, site=None):
+    """y = conv(x, w) + bias for NHWC x with a handful of channels (narrow_wrw_supported).  site: the layer object -- one marked
+    slim_blocks takes its data gradient on wc_conv_narrow_out_f32 (see NARROW_OUT)"""
     if _storage_extent(w) != w.numel():
         w = w.contiguous()
-    return _NarrowInConv.apply(x, w, bias)
+    return _NarrowInConv.apply(x, w, bias, site)
 
 
 def narrow_out_weight_gradient(x, gy, w):
@@ -1031,10 +1098,10 @@ class _Shape:
         self.shape = tuple(shape)
 
 
-def critic_block_plans(xshape, w1shape, w2shape, wsshape, down, ragged=False):
+def critic_block_plans(xshape, w1shape, w2shape, wsshape, down, ragged=False, blocks=False):
     """(plan of conv1, of conv2, of the shortcut | None) when the fused block takes these shapes, else None.  Shapes only: x NHWC,
     the weights (Cout, Cin, k, k), wsshape None for the identity shortcut, down = the block halves the grid; ragged: the block's layers
-    are marked ragged_conv (see supported)."""
+    are marked ragged_conv, blocks: slim_blocks (see supported)."""
     if len(xshape) != 4 or len(w1shape) != 4 or len(w2shape) != 4:
         return None
     N, H, W, C = xshape
@@ -1051,9 +1118,9 @@ def critic_block_plans(xshape, w1shape, w2shape, wsshape, down, ragged=False):
     if not (_colsum_ok(F1) and _colsum_ok(F2)):          # the bias gradients ride on the splits: no masked fp32 tensor to sum
         return None
     out = (N, H // 2, W // 2) if down else (N, H, W)
-    p1 = _plan('same', _Shape(xshape), _Shape(w1shape), ragged)
-    p2 = _plan('down3' if down else 'same', _Shape((N, H, W, F1)), _Shape(w2shape), ragged)
-    ps = _plan('same', _Shape(out + (C,)), _Shape(wsshape), ragged) if wsshape is not None else None
+    p1 = _plan('same', _Shape(xshape), _Shape(w1shape), ragged, False, blocks)
+    p2 = _plan('down3' if down else 'same', _Shape((N, H, W, F1)), _Shape(w2shape), ragged, False, blocks)
+    ps = _plan('same', _Shape(out + (C,)), _Shape(wsshape), ragged, False, blocks) if wsshape is not None else None
     if not (p1 and p1.ok and p2 and p2.ok and (wsshape is None or (ps and ps.ok))):
         return None
     return p1, p2, ps
@@ -1234,7 +1301,8 @@ class _CriticBlock(torch.autograd.Function):
 #           be used (_reader_record) and the grid fits the record (narrow_split_supported); else the two launches.
 #   MASK    when the image needs no gradient -- the critic's own updates -- the narrow weight gradient reads conv2's data gradient as it
 #           comes and h beside it (wc_conv_wrw_narrow_masked_f32); when it does, threshold_backward, MIOpen's data gradient and the plain
-#           entry run as before (the data gradient reads the masked copy anyway).
+#           entry run as before (the data gradient reads the masked copy anyway) -- unless conv1 is marked slim_blocks: then the image's
+#           gradient is the masked narrow-output launch (wc_conv_narrow_out_f32) and the route stays MASK.
 # conv2's launches, sites, roles and records are those of _FastConv; the shortcut and the block's add stay with the caller: same bits.
 # FIRST_BLOCK = False: the separate nodes; the two flags below switch one part each (tests, tools/first_block_bench.py).  Independent of
 # FUSED_BLOCK / FUSED_FINISH, which concern the blocks behind this one.
@@ -1356,7 +1424,13 @@ class _CriticFirstBlock(torch.autograd.Function):
         if need_h:
             k = w1.shape[2]
             want1 = need[1] or (ctx.has_bias[0] and need[2])
-            if need[0] or not FIRST_BLOCK_MASK:
+            if need[0] and FIRST_BLOCK_MASK and _narrow_out_route(conv1, dh.shape, w1.shape):
+                # the image's gradient on the MASK route as well: the narrow-output kernel reads conv2's data gradient as it comes and h beside
+                # it, as the weight gradient does -- no threshold_backward, no convolution_backward
+                dx = narrow_out_conv(dh, w1, mask=h)
+                if want1:
+                    dw1, db1 = narrow_gradients(x, dh, w1, ctx.has_bias[0], mask=h)
+            elif need[0] or not FIRST_BLOCK_MASK:
                 dh = torch.ops.aten.threshold_backward(dh, h, 0)
                 if need[0]:
                     dx = torch.ops.aten.convolution_backward(dh.permute(0, 3, 1, 2), x.permute(0, 3, 1, 2), w1, None, [1, 1], [k // 2, k // 2],

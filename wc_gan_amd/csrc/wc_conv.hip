@@ -1726,6 +1726,130 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_narrow_kernel(NarrowFwdArgs a
 template <int KS>
 __global__ __launch_bounds__(256, 2) void conv_fwd_narrow_split_kernel(NarrowFwdArgs a, NarrowSplitArgs s) { conv_fwd_narrow_body<KS, true>(a, &s); }
 
+// ---- 'same' convolution with a handful of OUTPUT channels: the data gradient of an image layer ---------------------------------------------
+//     out[n, y, x, c] = sum_{r,s} sum_o m(g)[n, y - (r - p), x - (s - p), o] w[o][c][r][s],   p = ks / 2,   c < Cn,   o < Cw
+// g is the wide tensor (the critic's first block: conv2's data gradient, 64 channels at 128 x 128) and m(g) = g or, with a mask tensor h
+// of g's shape, threshold_backward(g, h, 0) applied to the 16 bytes a lane has just loaded (wc_relu_mask_apply): the masked copy is never
+// written.  Counted directly -- rows = pixels, K = ks^2 Cw, Cn useful columns of 32 -- the product issues ks^2 times the MFMAs it needs.
+// Instead, per 32-pixel tile,
+//     Z[q][m] = sum_o m(g)[q][o] w[o][c][tap],   m = tap * Cn + c < 32
+// is Cw / 2 v_mfma_f32_32x32x2_f32 (rows = pixels; lane (i, k) loads the floats 8 j + 4 k .. + 3 of pixel i's row, and MFMA (j, e) reduces
+// channel 8 j + 4 k + e: any order of K serves as long as both operands use it), and
+//     out[q][c] = sum_tap Z[q - d(tap)][tap * Cn + c]
+// gathers from an LDS band of image rows.  A workgroup owns R output rows of one image and computes the Z of its ks / 2 halo rows itself
+// (those rows of g come out of the L2: the grid is laid out so that neighbouring bands run on one XCD).  The rows of a band are one
+// contiguous pixel range, so the tiles run over it flat, the last one partial (clamped loads, no stores).  The weight lies in LDS as
+// [Cw][32].  One pass over g (and h), no atomics, every sum in a fixed order: the same bits on every call.  fp32 throughout.
+struct NarrowOutArgs {
+    const float* g; const float* mask; const float* w; float* out;
+    int N, H, W, Cw, Cn, ks, nrow, ld;               // nrow = ks * ks * Cn (< 32); ld = floats per pixel of the band (odd: a thread per pixel meets no bank twice)
+    int R, bands;                                    // output rows per workgroup, workgroups per image
+    int nwg, per_xcd;                                // workgroup b of the grid works on band (b & 7) * per_xcd + (b >> 3)
+    int64_t sk, sn, sr, ss;                          // w[o * sk + c * sn + r * sr + s * ss]
+    unsigned magW, shW;
+};
+
+constexpr int kNarrowOutThreads = 512;
+constexpr int kNarrowOutLds = 80 * 1024;             // two workgroups per CU
+
+template <bool MASKED>
+__global__ __launch_bounds__(kNarrowOutThreads) void conv_narrow_out_kernel(NarrowOutArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float no_lds[];     // [Cw][32] weight rows | [band pixels][ld] Z
+    const int b = (int)(blockIdx.x & 7) * a.per_xcd + (int)(blockIdx.x >> 3);
+    if (b >= a.nwg) return;                                             // (the whole workgroup, in front of every barrier)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = lane & 31, k = lane >> 5;
+    const int n = b / a.bands, band = b - n * a.bands;
+    const int pad = a.ks >> 1;
+    const int y0 = band * a.R, y1 = min(y0 + a.R, a.H);
+    const int z0 = max(y0 - pad, 0), z1 = min(y1 + pad, a.H);          // the rows of Z the band's outputs read
+    float* wl = no_lds;
+    float* zl = no_lds + a.Cw * 32;
+    for (int e = tid; e < a.Cw * 32; e += kNarrowOutThreads) {
+        const int o = e >> 5, m = e & 31;
+        float v = 0.f;
+        if (m < a.nrow) {
+            const int tap = m / a.Cn, c = m - tap * a.Cn;
+            const int r = tap / a.ks, s = tap - r * a.ks;
+            v = a.w[o * a.sk + c * a.sn + r * a.sr + s * a.ss];
+        }
+        wl[e] = v;
+    }
+    __syncthreads();
+    const int64_t P0 = ((int64_t)n * a.H + z0) * a.W;                   // the band's first pixel
+    const int npix = (z1 - z0) * a.W;
+    const int ntiles = (npix + 31) >> 5, nch = a.Cw >> 5;
+    const int mine = wave < ntiles ? (ntiles - wave + 7) >> 3 : 0;      // this wave's tiles: wave, wave + 8, ...
+    const int steps = mine * nch;                                       // (tile, 32-channel chunk), the chunks of a tile in order
+    // lane (i, k): pixel i of the tile, the floats 8 j + 4 k .. + 3 of each chunk; a pixel past the band reads the band's last one
+    auto address = [&](int step) __attribute__((always_inline)) -> int64_t {
+        const int t = wave + 8 * (step / nch), ch = step % nch;
+        const int pl = min(t * 32 + i, npix - 1);
+        return (P0 + pl) * a.Cw + ch * 32 + 4 * k;
+    };
+    f32x4 gv[4], gn[4];
+    [[maybe_unused]] f32x4 mv[MASKED ? 4 : 1], mn[MASKED ? 4 : 1];
+    auto fetch = [&](int64_t at, f32x4 (&gd)[4], f32x4 (&md)[MASKED ? 4 : 1]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            gd[j] = *reinterpret_cast<const f32x4*>(a.g + at + 8 * j);
+            if constexpr (MASKED) md[j] = *reinterpret_cast<const f32x4*>(a.mask + at + 8 * j);
+        }
+    };
+    if (steps > 0) fetch(address(0), gv, mv);
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int step = 0; step < steps; ++step) {
+        if (step + 1 < steps) fetch(address(step + 1), gn, mn);         // one chunk ahead of the MFMAs that use it
+        const int ch = step % nch;
+        const float* wr = wl + (ch * 32 + 4 * k) * 32 + i;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if constexpr (MASKED) gv[j] = wc_relu_mask_apply(gv[j], mv[j]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(gv[j][e], wr[(8 * j + e) * 32], acc, 0, 0, 0);
+        }
+        if (ch == nch - 1) {
+            // rows = pixels (r & 3) + 8 (r >> 2) + 4 k of the tile, column m = i
+            const int t = wave + 8 * (step / nch);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int pz = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * k;
+                if (pz < npix && i < a.nrow) zl[pz * a.ld + i] = acc[r];
+                acc[r] = 0.f;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            gv[j] = gn[j];
+            if constexpr (MASKED) mv[j] = mn[j];
+        }
+    }
+    __syncthreads();
+    // a thread per output pixel: the taps in their order, then the channels
+    const int nout = (y1 - y0) * a.W;
+    for (int q = tid; q < nout; q += kNarrowOutThreads) {
+        const int qy = (int)(__umulhi((unsigned)q, a.magW) >> a.shW), xx = q - qy * a.W;
+        const int yy = y0 + qy;
+        float* op = a.out + (((int64_t)n * a.H + yy) * a.W + xx) * a.Cn;
+        for (int c = 0; c < a.Cn; ++c) {
+            float sum = 0.f;
+            for (int r = 0; r < a.ks; ++r) {
+                const int iy = yy - (r - pad);
+                for (int s = 0; s < a.ks; ++s) {
+                    const int ix = xx - (s - pad);
+                    if ((unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W)
+                        sum += zl[((iy - z0) * a.W + ix) * a.ld + (r * a.ks + s) * a.Cn + c];
+                }
+            }
+            op[c] = sum;
+        }
+    }
+}
+
 void magic_u31(unsigned d, unsigned* mag, unsigned* sh)
 {
     // q = umulhi(m, mag) >> sh == m / d for m < 2^31, d >= 2
@@ -2448,6 +2572,62 @@ int wc_conv_wrw_narrow_f32(const float* x, const float* gy, int64_t N, int64_t H
     if (!x || !gy || !dw || !ws) return WC_ERR_ARG;
     if (!wc_conv_wrw_narrow_supported(N, H, W, Cin, Cout, ksize)) return WC_ERR_SHAPE;
     return wc_conv_wrw_narrow64_f32(x, gy, N, H, W, Cin, Cout, ksize, dw, stride_k, stride_n, stride_r, stride_s, db, ws, ws_bytes, stream);
+}
+
+// the band plan of the narrow-output convolution: false where the weight rows and ks image rows of Z do not fit the workgroup's LDS
+static bool narrow_out_plan(NarrowOutArgs& a, int64_t N, int64_t H, int64_t W, int Cw, int Cn, int ksize)
+{
+    if (N <= 0 || H <= 0 || W < 2 || Cw <= 0 || Cn <= 0 || (ksize != 1 && ksize != 3)) return false;     // (W >= 2: the multiply-shift division)
+    if (ksize * ksize * Cn >= 32 || (Cw & 31)) return false;
+    if (N * H * W >= ((int64_t)1 << 31)) return false;
+    a.N = (int)N; a.H = (int)H; a.W = (int)W; a.Cw = Cw; a.Cn = Cn; a.ks = ksize;
+    a.nrow = ksize * ksize * Cn;
+    a.ld = a.nrow | 1;
+    const int halo = 2 * (ksize / 2);
+    const int64_t row_bytes = W * a.ld * (int64_t)sizeof(float);
+    const int64_t fit = ((int64_t)kNarrowOutLds - (int64_t)Cw * 32 * (int64_t)sizeof(float)) / row_bytes - halo;   // output rows that fit
+    if (fit < 1) return false;
+    int64_t bands = (H + fit - 1) / fit;
+    // a small batch: more, thinner bands (down to four rows behind a halo) until every CU has two workgroups
+    const int64_t thin = ksize == 1 ? H : (H + 3) / 4;
+    int64_t want = (512 + N - 1) / N;
+    if (want > thin) want = thin;
+    if (bands < want) bands = want;
+    a.R = (int)((H + bands - 1) / bands);
+    a.bands = (int)((H + a.R - 1) / a.R);
+    if (N * a.bands >= ((int64_t)1 << 28)) return false;
+    a.nwg = (int)(N * a.bands);
+    a.per_xcd = (a.nwg + 7) / 8;
+    magic_u31((unsigned)W, &a.magW, &a.shW);
+    return true;
+}
+
+int wc_conv_narrow_out_supported(int64_t N, int64_t H, int64_t W, int Cw, int Cn, int ksize)
+{
+    NarrowOutArgs a = {};
+    return narrow_out_plan(a, N, H, W, Cw, Cn, ksize) ? 1 : 0;
+}
+
+int wc_conv_narrow_out_f32(const float* g, const float* mask, const float* w, int64_t stride_k, int64_t stride_n, int64_t stride_r,
+                           int64_t stride_s, int64_t N, int64_t H, int64_t W, int Cw, int Cn, int ksize, float* out, wc_stream_t stream)
+{
+    if (!g || !w || !out) return WC_ERR_NULL;
+    NarrowOutArgs a = {};
+    if (!narrow_out_plan(a, N, H, W, Cw, Cn, ksize)) return WC_ERR_SHAPE;
+    if (((uintptr_t)g | (uintptr_t)mask) & 15) return WC_ERR_ARG;              // 16-byte loads of the wide rows
+    a.g = g; a.mask = mask; a.w = w; a.out = out;
+    a.sk = stride_k; a.sn = stride_n; a.sr = stride_r; a.ss = stride_s;
+    hipStream_t st = (hipStream_t)stream;
+    const int rows = a.R + 2 * (ksize / 2);
+    const size_t lds = ((size_t)Cw * 32 + (size_t)rows * a.W * a.ld) * sizeof(float);
+    const void* kernel = mask ? reinterpret_cast<const void*>(conv_narrow_out_kernel<true>)
+                              : reinterpret_cast<const void*>(conv_narrow_out_kernel<false>);
+    hipError_t e = wc_set_max_lds(kernel, lds);
+    if (e != hipSuccess) return (int)e;
+    const dim3 grid((unsigned)(8 * a.per_xcd));
+    if (mask) hipLaunchKernelGGL(conv_narrow_out_kernel<true>, grid, dim3(kNarrowOutThreads), lds, st, a);
+    else hipLaunchKernelGGL(conv_narrow_out_kernel<false>, grid, dim3(kNarrowOutThreads), lds, st, a);
+    return (int)hipGetLastError();
 }
 
 size_t wc_conv_wrw_workspace_bytes(const wc_conv_geom* g)

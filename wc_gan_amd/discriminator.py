@@ -2,7 +2,8 @@
 
 The discriminator holds NO whitening-and-coloring site in any shipped recipe (`--discriminator_norm`
 defaults to 'n', run.py:298), so it is the stock-torch part of the surrounding step: SN-ResNet blocks
-on the block convolutions of wc_gan_amd/conv.py (MIOpen for the 3-channel first layers) with the fused spectral-norm op
+on the block convolutions of wc_gan_amd/conv.py (the narrow kernels for the 3-channel first layers; their data gradient MIOpen's, or with
+slim_blocks=True the narrow-output kernel's) with the fused spectral-norm op
 (wc_gan_amd/spectral.py) standing in for gan.SNConv2D /
 SNDense / SNEmbeding (discriminator.py:26-33).  Three heads as in discriminator.py:73-85.
 
@@ -63,7 +64,7 @@ class ResBlockDown(nn.Module):
         from . import conv as fc
         return fc.critic_block_plans(xshape, tuple(self.conv1.conv.weight.shape), tuple(self.conv2.conv.weight.shape),
                                      tuple(self.shortcut.conv.weight.shape) if self.has_shortcut else None, self.resample == 'DOWN',
-                                     ragged=fc._ragged(self.conv1))
+                                     ragged=fc._ragged(self.conv1), blocks=fc._blocks(self.conv1))
 
     def _first_plan(self, x):
         """conv2's plan when the FIRST block's conv1 -> ReLU -> conv2 runs as one autograd node (conv.critic_first_block), else None: the
@@ -90,13 +91,13 @@ class ResBlockDown(nn.Module):
         if len(xshape) != 4 or tuple(w2.shape[2:]) != (3, 3) or w1.shape[0] <= 4:
             return None
         xs = fc._Shape(xshape)
-        p1 = fc._plan('same', xs, w1, fc._ragged(self.conv1))
+        p1 = fc._plan('same', xs, w1, fc._ragged(self.conv1), False, fc._blocks(self.conv1))
         if (p1 and p1.ok) or not fc.narrow_shapes_supported(xshape, tuple(w1.shape)):       # (a layer the block kernels take is not conv1 on images)
             return None
         if self.resample == 'DOWN' and (xshape[1] % 2 or xshape[2] % 2):
             return None
         hs = fc._Shape(tuple(xshape[:3]) + (w1.shape[0],))
-        p = fc._plan('down3' if self.resample == 'DOWN' else 'same', hs, w2, fc._ragged(self.conv2))
+        p = fc._plan('down3' if self.resample == 'DOWN' else 'same', hs, w2, fc._ragged(self.conv2), False, fc._blocks(self.conv2))
         return p if (p and p.ok) else None
 
     def takes_input_planes(self, xshape):
@@ -294,13 +295,13 @@ def make_discriminator(input_image_shape=(32, 32, 3), input_cls_shape=(1,), bloc
                        type='AC_GAN', norm='n', after_norm='n', spectral=False,
                        fully_diff_spectral=False, spectral_iterations=1, conv_singular=True,
                        sum_pool=False, dropout=False, arch='res', filters_emb=10, fused_tail=False, fused_projection=False,
-                       ragged_conv=False):
+                       ragged_conv=False, slim_blocks=False):
     """Keyword surface AND defaults of discriminator.py:15-20.  The shipped recipes pass type / spectral / sum_pool
     explicitly (run.py:230-233 from --gan_type, --discriminator_spectral, --sum_pool default 1), as wc_gan_amd.train's
     configs do.  `conv_singular=True` (the reference's default here; run.py:270 passes 0) asks for the
     convolution-operator singular value of SNConv2D, which this harness does not build: it warns and uses the
     reshaped-kernel sigma of the SN-GAN paper.  `fused_tail`, `fused_projection` (ours, default False): see Discriminator.
-    `ragged_conv` (ours, default False): marks every convolution layer -- see generator.Conv2D."""
+    `ragged_conv`, `slim_blocks` (ours, default False): mark every convolution layer -- see generator.Conv2D."""
     assert arch in ('res', 'dcgan')
     assert type in [None, 'AC_GAN', 'PROJECTIVE']
     if spectral and conv_singular:
@@ -308,7 +309,7 @@ def make_discriminator(input_image_shape=(32, 32, 3), input_cls_shape=(1,), bloc
         warnings.warn("conv_singular=True is not built: spectral normalisation uses the reshaped-kernel singular value",
                       stacklevel=2)
     sn_kw = dict(spectral_iterations=spectral_iterations, fully_diff_spectral=fully_diff_spectral)
-    conv_layer = partial(Conv2D, spectral=bool(spectral), conv_singular=conv_singular, ragged_conv=bool(ragged_conv), **sn_kw)
+    conv_layer = partial(Conv2D, spectral=bool(spectral), conv_singular=conv_singular, ragged_conv=bool(ragged_conv), slim_blocks=bool(slim_blocks), **sn_kw)
 
     def dense(i, o):        # SNDense / Dense (discriminator.py:29-30)
         if spectral:

@@ -106,7 +106,8 @@ class Conv2D(nn.Module):
     stride 2 (the DC critic's DOWN blocks): the 4x4 kernel only -- Keras 'same' then pads 1 and 1, torch's padding=1."""
 
     def __init__(self, in_channels, filters, kernel_size=(3, 3), use_bias=True, name=None, spectral=False,
-                 spectral_iterations=1, fully_diff_spectral=False, conv_singular=True, stride=1, ragged_conv=False, slim_conv=False):
+                 spectral_iterations=1, fully_diff_spectral=False, conv_singular=True, stride=1, ragged_conv=False, slim_conv=False,
+                 slim_blocks=False):
         super().__init__()
         # ragged_conv (ours): the block kernels may take this layer at a grid whose N*H*W is a multiple of 32 but not of 128, on a partial
         # last tile (conv.supported(ragged=True), DESIGN.md section 4.21); off, the layer keeps the routes it always had
@@ -115,6 +116,10 @@ class Conv2D(nn.Module):
         # ImageNet generator's 64- and 32-filter blocks; conv.supported(slim=True)).  The planes hand-overs do
         # not ask with the mark (takes_planes / takes_split): at these widths the site in front writes fp32 and the layer splits it
         self.slim_conv = bool(slim_conv)
+        # slim_blocks (ours): the critic's opt-in (make_discriminator(slim_blocks=True)) -- the block kernels may
+        # take this layer as 'same' or 'down3' at channel widths that are multiples of 64 (conv.supported(blocks=True)), and an image layer
+        # takes its data gradient on the narrow-output kernel (conv.NARROW_OUT)
+        self.slim_blocks = bool(slim_blocks)
         k = kernel_size if isinstance(kernel_size, int) else kernel_size[0]
         if stride not in (1, 2) or (stride == 2 and k != 4):
             raise ValueError(f"Conv2D: stride 2 is built for the 4x4 kernel ('same' = padding 1), not {k}x{k} / {stride}")
@@ -190,7 +195,7 @@ class Conv2D(nn.Module):
             if y is not None:
                 return y
         if x.is_cuda and self.kind == 'same' and fast_conv_mod.narrow_wrw_supported(x, w):
-            return fast_conv_mod.narrow_in_conv(x, w, c.bias)       # an image-like input: forward and weight / bias gradient on the fp32 matrix pipe (csrc/wc_conv.hip)
+            return fast_conv_mod.narrow_in_conv(x, w, c.bias, site=self)       # an image-like input: forward and weight / bias gradient on the fp32 matrix pipe (csrc/wc_conv.hip)
         return to_nhwc(c._conv_forward(to_nchw_view(x), w, c.bias))
 
     def forward_upsampled(self, x):

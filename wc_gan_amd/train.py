@@ -634,11 +634,28 @@ IMAGENET_SCHEDULES = {
 
 def slim_config(config, on=True):
     """The same recipe with every convolution layer of the GENERATOR marked slim_conv (make_generator(slim_conv=True), DESIGN.md section
-    4.22): the block kernels then take its 64- and 32-channel layers.  The critic has no such mark (its 64-wide layers would enter the fused
-    critic nodes, which have never run at that width).  A copy of any entry, the entry itself is left alone; on=False: the mark off."""
+    4.22): the block kernels then take its 64- and 32-channel layers.  The critic is never touched: its mark is slim_blocks, a name and a
+    helper of its own (slim_blocks_config).  A copy of any entry, the entry itself is left alone; on=False: the mark off."""
     import copy
     out = copy.deepcopy(config)
     out['generator'].update(slim_conv=bool(on))
+    return out
+
+
+# profiles/imagenet_critic_step.json (tools/imagenet_critic_step.py: the captured G+D step at batch 64 with the critic's mark on against the same
+# networks with it off, the generator marked slim_conv in both, 7 alternating rounds): the marked step is faster in every round (DESIGN.md
+# section 4.23)
+IMAGENET_SLIM_BLOCKS_SHIPS = True
+
+
+def slim_blocks_config(config, on=True):
+    """The same recipe with every convolution layer of the CRITIC marked slim_blocks (make_discriminator(slim_blocks=True), DESIGN.md
+    section 4.23): its 64-wide block layers run on the block kernels and the fused critic nodes, its image layers take their data gradient
+    on the narrow-output kernel.  The generator is left alone.  A copy of any entry, the entry itself is left alone; on=False: the mark
+    off.  The shipping form of the ImageNet recipe is slim_blocks_config(IMAGENET_CONFIGS['imagenet_cond_sa'], IMAGENET_SLIM_BLOCKS_SHIPS)."""
+    import copy
+    out = copy.deepcopy(config)
+    out['discriminator'].update(slim_blocks=bool(on))
     return out
 
 
