@@ -854,6 +854,24 @@ int wc_conv_bwd_pair_tail_f16x3(const void* ghi, const void* glo, const float* g
 int wc_conv_split_redo_masked_f32(const float* t, const float* a, int64_t n, float slope, void* hi, void* lo, float* scale, float* hist,
                                   wc_stream_t stream);
 
+/* The same convolutions with the k-split's shares summed INSIDE the workgroup: no partial sums in memory, no finish launch, no workspace.
+ * 64-point x 64-output tiles, one workgroup each; wave z computes the tile over share z of the (tap, chunk) loop, the four accumulators
+ * are added in LDS in share order and the workgroup finishes the values itself.  Every value has the bits of the entries above:
+ *   tail == NULL           wc_conv_f16x3 (res == NULL; relu as there) or wc_conv_res_f16x3 (res != NULL, relu == 0)
+ *   tail != NULL           wc_conv_tail_f16x3 (res == NULL and relu == 0: the residual travels in the tail).  SPLIT / MASKED: the planes, the
+ *                          scale word, the carried maximum and the FOLD of the record's pairs are those of that entry -- workgroup b of G
+ *                          writes the pairs b, b + G, ... with its own maximum, so single pairs differ and nothing reads a single pair.
+ *                          MASKED with colsum_partials: WC_ERR_SHAPE (the rows' summation order belongs to the 512-workgroup finish).
+ * wc_conv_local_supported: a whole-tile geometry (wc_conv_supported) whose tap loop is shared FOUR ways (the value wc_conv_workspace_bytes
+ * is computed from), Cout a multiple of 128 and not of 256, Cin a multiple of 64, and (N*H*W / 64) * nphase * (Cout / 64) workgroups at
+ * most the device's CU count (256 where no device is present) and at most 512 -- the critic's 128-channel layers at 8x8, batch 128.
+ * Elsewhere WC_ERR_SHAPE, nothing launched: the caller keeps the entries above, which keep their values and code.  Additive: WC_CORE_API
+ * keeps its list and WC_ABI_VERSION its value. */
+int wc_conv_local_supported(const wc_conv_geom* g);
+int wc_conv_local_f16x3(const void* xhi, const void* xlo, const float* xscale, const void* wimage, const float* wscale,
+                        const float* bias, const float* res, const void* zero_line, const wc_conv_geom* g, int relu, float* y,
+                        const wc_conv_tail* tail, wc_stream_t stream);
+
 /* Bandwidth yardstick used by bench.py: dst[i] = src[i] (float4 grid-stride copy), same stream rules. */
 int wc_stream_copy_f32(const float* src, float* dst, int64_t n, wc_stream_t stream);
 

@@ -185,6 +185,9 @@ SIGNATURES = {
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
                                             c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "wc_conv_split_redo_masked_f32": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wc_conv_local_supported": (c_int, [c_void_p]),
+    "wc_conv_local_f16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                    c_void_p, c_void_p, c_void_p]),
     "wc_std_stats_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "wc_std_stats_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "wc_std_factor_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_double, c_double, c_int, c_int, c_void_p, c_void_p,

@@ -134,7 +134,8 @@ def supported(x, w, kind, ragged=False, slim=False, blocks=False):
 class _Plan:
     """Everything about a call that depends on the shapes only, built once: the two geometries, the weight axes, the
     support verdict and the workspace sizes (the per-call host work is what is left: a few allocations and launches)."""
-    __slots__ = ('ok', 'fwd', 'bwd', 'fwd_ws', 'bwd_ws', 'wrw_ws', 'fwd_ptr', 'bwd_ptr', 'pair', 'res', 'tail', 'bwd_tail')
+    __slots__ = ('ok', 'fwd', 'bwd', 'fwd_ws', 'bwd_ws', 'wrw_ws', 'fwd_ptr', 'bwd_ptr', 'pair', 'res', 'tail', 'bwd_tail', 'local',
+                 'bwd_local')
 
     def __init__(self, kind, N, H, W, wshape, ragged=False, slim=False):
         class _W:                                 # shape-only stand-in for the weight
@@ -160,6 +161,9 @@ class _Plan:
         # a finish launch that can go on to its follower's work (wc_conv_tail_f16x3): the forward's, the data gradient's
         self.tail = self.ok and bool(lib.wc_conv_tail_supported(self.fwd_ptr))
         self.bwd_tail = self.ok and bool(lib.wc_conv_tail_supported(self.bwd_ptr))
+        # the k-split's shares summed inside the workgroup (wc_conv_local_f16x3): one launch where run / run_tail issued two (LOCAL_KSPLIT)
+        self.local = self.ok and bool(lib.wc_conv_local_supported(self.fwd_ptr))
+        self.bwd_local = self.ok and bool(lib.wc_conv_local_supported(self.bwd_ptr))
 
 
 _plans = {}
@@ -545,6 +549,19 @@ def finish_images(root):
     _clear_images(root)
 
 
+# A k-split convolution whose shares fit one workgroup's waves (wc_conv_local_supported; _Plan.local / .bwd_local: the critic's 128-channel
+# layers at 8x8, batch 128) runs as ONE launch that sums the shares in LDS and finishes them (csrc/wc_conv.hip conv_local_kernel; DESIGN.md
+# section 4.5) instead of the convolution and a finish launch over 16 MiB of partial sums.  Same bits.  False: the two launches everywhere
+# (tests, tools/local_ksplit_bench.py).
+LOCAL_KSPLIT = True
+
+
+def _local(lib, geom, tail=None):
+    if not LOCAL_KSPLIT or (tail is not None and tail.c.kind == _lib.TAIL_MASKED and tail.c.colsum_partials):
+        return False
+    return bool(lib.wc_conv_local_supported(ctypes.addressof(geom)))
+
+
 def run(planes, image, geom, bias=None, relu=False, nbytes=None, res=None):
     """res: a tensor of the output's shape added to the result in the convolution's finish (wc_conv_res_f16x3: the geometries
     wc_conv_res_supported takes, _Plan.res)"""
@@ -552,6 +569,13 @@ def run(planes, image, geom, bias=None, relu=False, nbytes=None, res=None):
     img, ws = image
     lib = _lib.load()
     y = torch.empty((geom.N, geom.Hout, geom.Wout, geom.Cout), dtype=torch.float32, device=hi.device)
+    if _local(lib, geom):
+        if res is not None and (relu or not (res.is_contiguous() and res.shape == y.shape and res.dtype == torch.float32 and res.device == y.device)):
+            raise ValueError("run: the residual is a dense fp32 tensor of the output's shape (and there is no ReLU behind it)")
+        _lib.check(lib.wc_conv_local_f16x3(_ptr(hi), _ptr(lo), _ptr(xs), _ptr(img), _ptr(ws), _ptr(bias) if bias is not None else None,
+                                           _ptr(res) if res is not None else None, _ptr(_zero_line(hi.device)), ctypes.addressof(geom),
+                                           1 if relu else 0, _ptr(y), None, _stream()), "wc_conv_local_f16x3")
+        return y
     if nbytes is None:
         nbytes = lib.wc_conv_workspace_bytes(ctypes.addressof(geom))
     work = torch.empty(nbytes, dtype=torch.uint8, device=hi.device) if nbytes else None
@@ -666,6 +690,11 @@ def run_tail(planes, image, geom, tail, bias=None, nbytes=None):
     y = None
     if tail.c.kind != _lib.TAIL_DX:
         y = torch.empty((geom.N, geom.Hout, geom.Wout, geom.Cout), dtype=torch.float32, device=hi.device)
+    if _local(lib, geom, tail):
+        _lib.check(lib.wc_conv_local_f16x3(_ptr(hi), _ptr(lo), _ptr(xs), _ptr(img), _ptr(ws), _ptr(bias) if bias is not None else None,
+                                           None, _ptr(_zero_line(hi.device)), ctypes.addressof(geom), 0, _ptr(y),
+                                           ctypes.addressof(tail.c), _stream()), "wc_conv_local_f16x3")
+        return y
     if nbytes is None:
         nbytes = lib.wc_conv_workspace_bytes(ctypes.addressof(geom))
     work = torch.empty(nbytes, dtype=torch.uint8, device=hi.device) if nbytes else None

@@ -31,6 +31,8 @@
 //     the kernels' bodies are __device__ functions of the block coordinates, shared with the launches of their own; same bits.
 //   * where a k-split's finish was followed by a launch that read its result back only to re-express it (the critic at 8x8), the finish does
 //     that work too: the reader's planes, or the block input's gradient (conv_finish_tail_kernel, conv_pair_reduce_tail_kernel); same bits.
+//   * where such a k-split has four shares and its 64 x 64 tiles fit the chip one per CU (the critic at 8x8, batch 128), the shares are the
+//     four WAVES of a workgroup and meet in LDS: one launch, no partial sums in memory (conv_local_kernel); same bits.
 //   * conv(relu(x)) and conv(leaky_relu(x)) apply the activation while x is split (conv_split_*_kernel, split_act).
 // MFMA-bound by design: 3 * 2*M*Cout*K flop on the fp16 pipe against 2*M*Cout*K on the fp32 pipe (157 TFLOP/s peak).
 #include "wc_common.h"
@@ -404,19 +406,25 @@ struct KsplitReduceArgs {
 // the finished value of float4 i: (sum of the shares in order) * inv + bias (, ReLU) (+ res).  ONE source for every kernel that finishes a
 // k-split -- the plain finish below and the finishes that go on to write what the next launch used to read back (conv_finish_split_body,
 // conv_finish_dx_body): whether `v * inv` and `+ bias` contract is decided here, for all of them
+// SUMMED: the caller has added the shares itself, in this order, and hands the sum in as `v` (conv_local_kernel: its shares meet in LDS);
+// the existing callers instantiate the function as it always was
+template <bool SUMMED = false>
 __device__ __forceinline__ f32x4 conv_ksplit_finish_elem(const float* __restrict__ partial, int ksplit, int64_t n4, int cout, const float inv,
-                                                         const float* __restrict__ bias, int relu, const float* __restrict__ res, const int64_t i)
+                                                         const float* __restrict__ bias, int relu, const float* __restrict__ res, const int64_t i,
+                                                         f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f})
 {
-    f32x4 v = *reinterpret_cast<const f32x4*>(partial + 4 * i);
-    int z = 1;
-    for (; z + 3 < ksplit; z += 4) {                 // four shares in flight, added in order
-        f32x4 t[4];
-        #pragma unroll
-        for (int u = 0; u < 4; ++u) t[u] = *reinterpret_cast<const f32x4*>(partial + 4 * ((z + u) * n4 + i));
-        #pragma unroll
-        for (int u = 0; u < 4; ++u) v += t[u];
+    if constexpr (!SUMMED) {
+        v = *reinterpret_cast<const f32x4*>(partial + 4 * i);
+        int z = 1;
+        for (; z + 3 < ksplit; z += 4) {                 // four shares in flight, added in order
+            f32x4 t[4];
+            #pragma unroll
+            for (int u = 0; u < 4; ++u) t[u] = *reinterpret_cast<const f32x4*>(partial + 4 * ((z + u) * n4 + i));
+            #pragma unroll
+            for (int u = 0; u < 4; ++u) v += t[u];
+        }
+        for (; z < ksplit; ++z) v += *reinterpret_cast<const f32x4*>(partial + 4 * (z * n4 + i));
     }
-    for (; z < ksplit; ++z) v += *reinterpret_cast<const f32x4*>(partial + 4 * (z * n4 + i));
     v = v * inv;
     if (bias) v += *reinterpret_cast<const f32x4*>(bias + (4 * i) % cout);
     if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
@@ -426,6 +434,13 @@ __device__ __forceinline__ f32x4 conv_ksplit_finish_elem(const float* __restrict
         for (int j = 0; j < 4; ++j) v[j] = __fadd_rn(v[j], r[j]);        // (its own rounding: never contracted into the line above)
     }
     return v;
+}
+
+// "finish the sum": the second half alone
+__device__ __forceinline__ f32x4 conv_ksplit_finish_sum(const f32x4 v, int cout, const float inv, const float* __restrict__ bias, int relu,
+                                                        const float* __restrict__ res, const int64_t i)
+{
+    return conv_ksplit_finish_elem<true>(nullptr, 0, 0, cout, inv, bias, relu, res, i, v);
 }
 
 __device__ __forceinline__ void conv_ksplit_reduce_body(const float* __restrict__ partial, int ksplit, int64_t n4, int cout,
@@ -862,6 +877,208 @@ __global__ __launch_bounds__(256) void conv_split_redo_kernel(const float* __res
         for (int j = 0; j < 4; ++j) { h[j] = (_Float16)v[j]; l[j] = (_Float16)(v[j] - (float)h[j]); }
         *reinterpret_cast<f16x4*>(hi + 4 * i) = h;
         *reinterpret_cast<f16x4*>(lo + 4 * i) = l;
+    }
+}
+
+// ---- a k-split whose shares meet inside the workgroup (wc_conv_local_f16x3: the critic's 128-channel layers at 8x8, k-split 4) ----------------
+// conv_f16x3_kernel<2, 2, true> gives share z of the (tap, chunk) loop to blockIdx.z: 4 x 4 MiB of raw sums go to memory and a second launch
+// reads them back.  Here the tensor is cut into 64-point x 64-output tiles, one workgroup each (256 at the critic's shape: one per CU), and
+// WAVE z computes the whole tile over share z: the four accumulators meet in LDS, are added in share order ((p0 + p1) + p2) + p3 and the
+// workgroup finishes the values itself (conv_ksplit_finish_sum: conv_ksplit_finish_elem's second half) and goes on to the tail's work with
+// the functions the finish launches call -- no workspace, no second launch, nothing between workgroups.  Same bits: a wave's accumulator
+// element sees the products of conv_f16x3_body<2, 2, true>'s -- iterations [z iters / 4, (z + 1) iters / 4) ascending, k-step 0 then 1,
+// lo*hi, hi*lo, hi*hi -- through the same fragment images, so it holds that kernel's partial sum; the tile shape does not enter.
+// Staging is private to the wave (2 stages x 16 KiB: A = 2 m-blocks, B = 2 n-blocks, each x 2 k-steps x hi | lo; 128 KiB per workgroup),
+// so the loop has NO workgroup barrier, only the wave's own counted vmcnt waits (LDS-DMAs retire in issue order): a pipeline of half
+// iterations -- while the MFMAs of k-step h run, the 8 DMAs of k-step h + 2 go out between them (into the 1-KiB slots k-step h - 2 was
+// read from during k-step h - 3) and, once 6 of them are out, vmcnt(6) says k-step h + 1 has landed and its fragments are read.
+// SPLIT / MASKED: workgroup b writes the pairs b, b + G, ... of the reader's record with its own maximum (conv_fwd_narrow_split_kernel's
+// idiom): the record folds to the same maximum, so the next call takes the same scale.  MASKED without partial rows only: another
+// assignment of elements to the 512 rows would change the bias gradient's summation order (the host refuses).
+enum { kTailNone = 0 };
+constexpr int kLocalWaveBytes = 32 * 1024;          // a wave's two stages; after the loop its 64 x 64 accumulator image (64 x kLocalLd floats)
+constexpr int kLocalLd = 64 + 4;                    // floats per row of that image (16-byte aligned rows, the lane halves 16 banks apart)
+
+template <int KIND>
+__global__ __launch_bounds__(256) void conv_local_kernel(ConvArgs a, FinishTailArgs f)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int A_BYTES = 8 * 1024, STAGE = 16 * 1024;
+    constexpr bool PLANES = KIND == kTailSplit || KIND == kTailMasked;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // = the share z
+    const int ntn = a.Cout >> 6;
+    const int phase = blockIdx.y / ntn, nt = blockIdx.y - phase * ntn;
+    const unsigned m0 = blockIdx.x * 64;
+    const unsigned HW = a.H * a.W;
+    const int koff = (lane >> 5) * 8;
+    [[maybe_unused]] const unsigned bid = blockIdx.y * gridDim.x + blockIdx.x;
+
+    int gy[2], gx[2];
+    unsigned gpix[2];                               // input pixel index of (n, 0, 0)
+    #pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const unsigned m = m0 + q * 32 + (lane & 31);
+        const unsigned n = __umulhi(m, a.magHW) >> a.shHW, rem = m - n * HW;
+        const unsigned yy = __umulhi(rem, a.magW) >> a.shW, xx = rem - yy * a.W;
+        gy[q] = yy * a.in_stride; gx[q] = xx * a.in_stride; gpix[q] = n * (a.Hin * a.Win);
+    }
+    const unsigned lds0 = (unsigned)(size_t)((__attribute__((address_space(3))) char*)smem) + wave * kLocalWaveBytes;
+    const char* const wbase = smem + wave * kLocalWaveBytes;
+    const int nchunk = a.Cin >> 5;
+    const int iters = a.ntaps * nchunk;
+    const int nblk_all = a.Cout >> 5;
+
+    f32x16 acc[2][2];
+    #pragma unroll
+    for (int i = 0; i < 2; ++i)
+        #pragma unroll
+        for (int j = 0; j < 2; ++j)
+            #pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    const int it0 = wave * iters / 4, it1 = (wave + 1) * iters / 4;
+    int tabv = 0;                                   // lane t: packed (dy, dx) of tap t of this phase
+    if (lane < a.ntaps) tabv = (a.dy[phase][lane] & 0xff) | ((a.dx[phase][lane] & 0xff) << 8);
+    const char* pa[2][2];                           // next iteration: hi / lo source of this lane's A rows (k-step 0)
+    int pstep[2];                                   // bytes to k-step 1 (0 on the zero line)
+    const char* pw;                                 // next iteration: this lane's 16 bytes of the first weight chunk
+    unsigned sb_next = 0;
+    auto prep = [&](int it, int stage) {
+        const int tap = it / nchunk, ch = it - tap * nchunk;
+        const int p = __builtin_amdgcn_readlane(tabv, tap);
+        const int dy = (signed char)(p & 0xff), dx = (signed char)((p >> 8) & 0xff);
+        #pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int iy = gy[q] + dy, ix = gx[q] + dx;
+            const bool ok = (unsigned)iy < (unsigned)a.Hin && (unsigned)ix < (unsigned)a.Win;
+            const int64_t e = ((int64_t)(gpix[q] + iy * a.Win + ix)) * a.Cin + ch * 32 + koff;
+            pa[q][0] = reinterpret_cast<const char*>(ok ? a.xhi + e : a.zero + koff);
+            pa[q][1] = reinterpret_cast<const char*>(ok ? a.xlo + e : a.zero + koff);
+            pstep[q] = ok ? 32 : 0;
+        }
+        pw = a.wimg + ((((int64_t)(phase * a.ntaps + tap) * nchunk + ch) * nblk_all + nt * 2) << 12) + lane * 16;
+        sb_next = __builtin_amdgcn_readfirstlane(lds0 + stage * STAGE);
+    };
+    // DMA d of an iteration: k-step d >> 3 first; inside a k-step the rows' four chunks (m-block, hi | lo), then the weights' four
+    // (n-block, hi | lo) -- the chunk order of the fragment images, so a k-step's eight DMAs are all that k-step's fragment reads need
+    auto dma = [&](int d) {
+        const int ks = d >> 3, e = d & 7;
+        if (e < 4) {
+            const int q = e >> 1, pl = e & 1;
+            lds_dma16(pa[q][pl] + ks * pstep[q], sb_next + ((q * 2 + ks) * 2 + pl) * 1024);
+        } else {
+            const int idx = (((e - 4) >> 1) * 2 + ks) * 2 + (e & 1);
+            lds_dma16(pw + idx * 1024, sb_next + A_BYTES + idx * 1024);
+        }
+    };
+    f16x8 fa[2][2][2], fb[2][2][2];                 // [k-step][block][hi | lo]
+    auto frags = [&](int stage, int ks) {
+        const char* sa = wbase + stage * STAGE + lane * 16;
+        const char* sb = sa + A_BYTES;
+        #pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const char* p = sa + ((i * 2 + ks) * 2) * 1024;
+            fa[ks][i][0] = *reinterpret_cast<const f16x8*>(p);
+            fa[ks][i][1] = *reinterpret_cast<const f16x8*>(p + 1024);
+        }
+        #pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const char* p = sb + ((j * 2 + ks) * 2) * 1024;
+            fb[ks][j][0] = *reinterpret_cast<const f16x8*>(p);
+            fb[ks][j][1] = *reinterpret_cast<const f16x8*>(p + 1024);
+        }
+    };
+    prep(it0, 0);
+    #pragma unroll
+    for (int d = 0; d < 16; ++d) dma(d);
+    // (the record's 8 KB are read behind the first stage's DMAs: one wait covers both)
+    [[maybe_unused]] HistPick pk = {0, 0, 1.0f};
+    if constexpr (PLANES) pk = conv_hist_pick(f.hist, f.scale_out, bid);
+    __builtin_amdgcn_s_waitcnt(0x0F78);            // vmcnt(8): k-step 0 of the first iteration has landed
+    frags(0, 0);
+    for (int it = it0; it < it1; ++it) {
+        const int stage = (it - it0) & 1;
+        __builtin_amdgcn_sched_barrier(0);
+        #pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            #pragma unroll
+            for (int g = 0; g < 12; ++g) {
+                const int prod = g >> 2, i = (g >> 1) & 1, j = g & 1;
+                // lo*hi, hi*lo, hi*hi
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ks][i][prod == 0 ? 1 : 0], fb[ks][j][prod == 1 ? 1 : 0], acc[i][j], 0, 0, 0);
+                if (ks == 0 && g == 0) {
+                    // the last iteration re-fetches its own data into the idle stage: no branch in the loop, nobody uses it
+                    prep(it + 1 < it1 ? it + 1 : it, stage ^ 1);
+                }
+                if (g % 3 != 2) {
+                    dma(ks * 8 + g - g / 3);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (g == 7) {
+                    __builtin_amdgcn_s_waitcnt(0x0F76);        // vmcnt(6): all but this half's six DMAs -- the next k-step has landed
+                    if (ks == 0) frags(stage, 1);
+                    else frags(stage ^ 1, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);            // the idle stage's last DMAs: the wave's LDS is its own to overwrite
+    // the wave's 64 x 64 accumulator -> its own LDS, rows = points, columns = outputs of the tile
+    {
+        float* tl = reinterpret_cast<float*>(smem + wave * kLocalWaveBytes);
+        #pragma unroll
+        for (int i = 0; i < 2; ++i)
+            #pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                #pragma unroll
+                for (int j = 0; j < 2; ++j) tl[row * kLocalLd + j * 32 + (lane & 31)] = acc[i][j][r];
+            }
+    }
+    __syncthreads();
+    // finish: thread t takes the float4 (row t / 16 + 16 k, columns 4 (t % 16) ..) of the tile, k = 0..3: a 256-byte row of y per 16 lanes
+    const float inv = 1.0f / (a.xscale[0] * a.wscale[0]);
+    const int oy0 = a.offy[phase], ox0 = a.offx[phase];
+    [[maybe_unused]] float amax = 0.f;
+    #pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int row = (tid >> 4) + 16 * k;
+        const float* p = reinterpret_cast<const float*>(smem) + row * kLocalLd + 4 * (tid & 15);
+        f32x4 v = *reinterpret_cast<const f32x4*>(p);
+        #pragma unroll
+        for (int z = 1; z < 4; ++z) v += *reinterpret_cast<const f32x4*>(p + z * (kLocalWaveBytes / 4));      // ((p0 + p1) + p2) + p3
+        const unsigned m = m0 + row;
+        const unsigned n = __umulhi(m, a.magHW) >> a.shHW, rem = m - n * HW;
+        const unsigned yy = __umulhi(rem, a.magW) >> a.shW, xx = rem - yy * a.W;
+        const int64_t opix = ((int64_t)n * a.Hout + (yy * a.out_stride + oy0)) * a.Wout + (xx * a.out_stride + ox0);
+        const int64_t i4 = (opix * a.Cout + nt * 64 + 4 * (tid & 15)) >> 2;
+        v = conv_ksplit_finish_sum(v, f.k.cout, inv, f.k.bias, f.k.relu, KIND == kTailSplit || KIND == kTailNone ? f.res : nullptr, i4);
+        if constexpr (KIND == kTailDx) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(f.mask + 4 * i4);
+            const f32x4 o = *reinterpret_cast<const f32x4*>(f.other + 4 * i4);
+            *reinterpret_cast<f32x4*>(f.out + 4 * i4) = conv_block_dx_elem<false>(v, x, o);
+        } else {
+            *reinterpret_cast<f32x4*>(f.k.y + 4 * i4) = v;
+            if constexpr (KIND == kTailMasked) v = wc_mask_apply(v, *reinterpret_cast<const f32x4*>(f.mask + 4 * i4), 0.f);
+            if constexpr (KIND == kTailSplit) v = split_act(v, 1, 0.f);
+            if constexpr (PLANES) amax = conv_split_elem(v, amax, pk.s, f.hi, f.lo, i4);
+        }
+    }
+    if constexpr (PLANES) {
+        // publish (conv_hist_publish's fold and 8-byte store): the workgroup's pairs of the OTHER array
+        typedef float f32x2h __attribute__((ext_vector_type(2)));
+        __shared__ float red[4];
+        #pragma unroll
+        for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+        if (lane == 0) red[wave] = amax;
+        __syncthreads();
+        const f32x2h pr = {fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), __builtin_bit_cast(float, pk.tag)};
+        const unsigned G = gridDim.x * gridDim.y;
+        for (unsigned pair = bid + tid * G; pair < (unsigned)kAmaxBlocks; pair += 256u * G)
+            *reinterpret_cast<f32x2h*>(f.hist + (1 - pk.src) * kHistArray + 2 * pair) = pr;
     }
 }
 
@@ -2229,7 +2446,8 @@ static bool conv_big_tile(const wc_conv_geom* g, int ksplit)
 
 // argument checks and the kernel's argument block of wc_conv_f16x3 (shared with wc_conv_bwd_pair_f16x3)
 static int conv_prepare(ConvArgs& a, const void* xhi, const void* xlo, const float* xscale, const void* wimage, const float* wscale,
-                        const float* bias, const void* zero_line, const wc_conv_geom* g, int relu, float* y, void* ws, size_t ws_bytes)
+                        const float* bias, const void* zero_line, const wc_conv_geom* g, int relu, float* y, void* ws, size_t ws_bytes,
+                        bool need_ws = true)
 {
     if (!xhi || !xlo || !xscale || !wimage || !wscale || !zero_line || !g || !y) return WC_ERR_ARG;
     if (!conv_takes(g)) return WC_ERR_SHAPE;
@@ -2241,7 +2459,7 @@ static int conv_prepare(ConvArgs& a, const void* xhi, const void* xlo, const flo
     a.ksplit = conv_ksplit(g); a.partial = (float*)ws;
     magic_u31((unsigned)(g->H * g->W), &a.magHW, &a.shHW);
     magic_u31((unsigned)g->W, &a.magW, &a.shW);
-    if (a.ksplit > 1 && (!ws || ws_bytes < wc_conv_workspace_bytes(g))) return WC_ERR_WORKSPACE;
+    if (need_ws && a.ksplit > 1 && (!ws || ws_bytes < wc_conv_workspace_bytes(g))) return WC_ERR_WORKSPACE;
     for (int p = 0; p < kMaxPhase; ++p) {
         a.offy[p] = g->off_y[p]; a.offx[p] = g->off_x[p];
         for (int t = 0; t < kMaxTaps; ++t) { a.dy[p][t] = g->dy[p][t]; a.dx[p][t] = g->dx[p][t]; }
@@ -2368,6 +2586,65 @@ int wc_conv_tail_f16x3(const void* xhi, const void* xlo, const float* xscale, co
     const hipError_t e2 = hipGetLastError();
     if (e2 != hipSuccess) return (int)e2;
     return tail_redo(tail, f, st);
+}
+
+// ---- the k-split's shares summed inside the workgroup (conv_local_kernel): wc_conv_local_supported, wc_conv_local_f16x3 ------------------
+// the device's CU count; without a device (a predicate asked on a build machine) gfx950's 256
+static int local_cus()
+{
+    static int cus = 0;
+    if (cus > 0) return cus;
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 256;
+    return cus = n;
+}
+
+int wc_conv_local_supported(const wc_conv_geom* g)
+{
+    if (!wc_conv_supported(g)) return 0;            // whole tiles: no ragged grid
+    if ((g->Cout % 128) != 0 || (g->Cout % 256) == 0 || (g->Cin % 64) != 0) return 0;
+    if (conv_ksplit(g) != 4) return 0;              // four waves = four shares (eight wave-private double stages do not fit the LDS)
+    const int64_t wgs = ((int64_t)g->N * g->H * g->W / 64) * g->nphase * (g->Cout / 64);
+    return wgs <= local_cus() && wgs <= kAmaxBlocks;        // one workgroup (128 KiB of LDS) per CU; a pair of the reader's record each
+}
+
+int wc_conv_local_f16x3(const void* xhi, const void* xlo, const float* xscale, const void* wimage, const float* wscale,
+                        const float* bias, const float* res, const void* zero_line, const wc_conv_geom* g, int relu, float* y,
+                        const wc_conv_tail* tail, wc_stream_t stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const int kind = tail ? tail->kind : kTailNone;
+    if (tail && kind == WC_CONV_TAIL_DX && !tail->out) return WC_ERR_NULL;
+    if ((res && relu) || (tail && (res || relu))) return WC_ERR_ARG;        // (a tail brings its own residual; no ReLU in front of either)
+    ConvArgs a;
+    float* y_or_out = kind == WC_CONV_TAIL_DX ? tail->out : y;              // (DX: no fp32 copy of the convolution's own output)
+    const int rc = conv_prepare(a, xhi, xlo, xscale, wimage, wscale, bias, zero_line, g, relu, y_or_out, nullptr, 0, false);
+    if (rc != WC_OK) return rc;
+    if (!wc_conv_local_supported(g)) return WC_ERR_SHAPE;
+    FinishTailArgs f;
+    if (tail) {
+        const int rt = tail_prepare(f, tail, a, g, xscale, wscale, bias, y, nullptr);
+        if (rt != WC_OK) return rt;
+        if (f.colsum) return WC_ERR_SHAPE;          // (the partial rows' summation order belongs to the 512 x 256 grid)
+    } else {
+        memset(&f, 0, sizeof(f));
+        f.k.cout = g->Cout; f.k.bias = bias; f.k.relu = relu; f.k.y = y; f.res = res;
+    }
+    constexpr int LDS = 4 * kLocalWaveBytes;
+    const void* kernel = kind == WC_CONV_TAIL_SPLIT ? reinterpret_cast<const void*>(conv_local_kernel<kTailSplit>)
+                       : kind == WC_CONV_TAIL_MASKED ? reinterpret_cast<const void*>(conv_local_kernel<kTailMasked>)
+                       : kind == WC_CONV_TAIL_DX ? reinterpret_cast<const void*>(conv_local_kernel<kTailDx>)
+                       : reinterpret_cast<const void*>(conv_local_kernel<kTailNone>);
+    const hipError_t e = wc_set_max_lds(kernel, LDS);
+    if (e != hipSuccess) return (int)e;
+    const dim3 grid((unsigned)((int64_t)g->N * g->H * g->W / 64), (unsigned)(g->nphase * (g->Cout / 64)));
+    if (kind == WC_CONV_TAIL_SPLIT) hipLaunchKernelGGL((conv_local_kernel<kTailSplit>), grid, dim3(256), LDS, st, a, f);
+    else if (kind == WC_CONV_TAIL_MASKED) hipLaunchKernelGGL((conv_local_kernel<kTailMasked>), grid, dim3(256), LDS, st, a, f);
+    else if (kind == WC_CONV_TAIL_DX) hipLaunchKernelGGL((conv_local_kernel<kTailDx>), grid, dim3(256), LDS, st, a, f);
+    else hipLaunchKernelGGL((conv_local_kernel<kTailNone>), grid, dim3(256), LDS, st, a, f);
+    const hipError_t e2 = hipGetLastError();
+    if (e2 != hipSuccess) return (int)e2;
+    return tail ? tail_redo(tail, f, st) : WC_OK;
 }
 
 int wc_conv_block_dx_f32(const float* dx1, const float* x, const float* other, int64_t N, int64_t H, int64_t W, int C, int down,
