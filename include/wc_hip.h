@@ -787,6 +787,39 @@ int    wc_conv_narrow_out_f32(const float* g, const float* mask /*nullable*/, co
                               int64_t stride_r, int64_t stride_s, int64_t N, int64_t H, int64_t W, int Cw, int Cn, int ksize,
                               float* out, wc_stream_t stream);
 
+/* ==== the narrow kernels at a wide side of 32 channels: the ImageNet generator's last layer, 32 -> 3 at 128 x 128 ========
+ * Additive: WC_CORE_API keeps its list and WC_ABI_VERSION its value; every entry above keeps its signature, its kernel and its answers,
+ * and the narrow64 / narrow predicates and workspace functions still decline what they declined.
+ *
+ * wc_conv_narrow32_supported: wc_conv_narrow64_supported with Cout % 32 == 0 in place of % 64 -- ksize in {1, 3}, ksize^2 * Cin < 32,
+ * W >= 2, N*H*W < 2^31.  A superset.
+ *
+ * wc_conv_wrw_narrow32_f32 / wc_conv_wrw_narrow32_workspace_bytes: wc_conv_wrw_narrow64_f32's contract on that set.  Cout % 64 == 0: the
+ * launches, the bits and the workspace size of wc_conv_wrw_narrow64_f32.  Cout % 64 == 32: a kernel whose channel group is 32 wide --
+ * lane (i, k) loads the one float gy[p + k][32 grp + i], one v_mfma_f32_32x32x2_f32 per pixel pair -- and EVERY group of such a layer is
+ * 32 wide (Cout = 96: three groups; 160: five), not 128-groups plus a remainder: one kernel and one element map per layer.  The same
+ * pixel ranges, the same fold of a workgroup's eight waves and the same fixed order over the partials; no atomics, the same bits on
+ * every call.
+ *
+ * wc_conv_fwd_narrow32_f32: wc_conv_fwd_narrow_f32's contract (negative strides, the bias as a row of the product, relu) on that set, with
+ * N*H*W*Cin < 2^31 as there.  Cout % 64 == 0: that entry's launch and bits.  Cout % 64 == 32: the same body with one 32-channel block per
+ * wave; a wave's tile leaves as 16-byte stores of whole 128-byte pixel rows. */
+int    wc_conv_narrow32_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize);
+size_t wc_conv_wrw_narrow32_workspace_bytes(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize);
+int    wc_conv_wrw_narrow32_f32(const float* x, const float* gy, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize,
+                                float* dw, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s, float* db /*nullable*/,
+                                void* ws, size_t ws_bytes, wc_stream_t stream);
+int    wc_conv_fwd_narrow32_f32(const float* x, const float* w, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
+                                const float* bias /*nullable*/, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize, int relu,
+                                float* y, wc_stream_t stream);
+
+/* wc_conv_narrow_out_f32 with bias[c] (Cn floats, nullable) added to each output behind its tap sum: the forward of a layer with few
+ * outputs, bias included, in one launch.  bias == NULL: wc_conv_narrow_out_f32 itself, its kernels and its bits; with a bias the bits of
+ * that result followed by one fp32 add. */
+int    wc_conv_narrow_out_bias_f32(const float* g, const float* mask /*nullable*/, const float* w, int64_t stride_k, int64_t stride_n,
+                                   int64_t stride_r, int64_t stride_s, const float* bias /*nullable*/, int64_t N, int64_t H, int64_t W,
+                                   int Cw, int Cn, int ksize, float* out, wc_stream_t stream);
+
 /* wc_conv_wrw_f16x3 plus the bias gradient db[Cout] = column sums of gy, from the partial rows wc_conv_split_colsum_f32
  * left while gy was split (fixed summation order, no extra launch). */
 int wc_conv_wrw_bias_f16x3(const void* xhi, const void* xlo, const float* xscale, const void* ghi, const void* glo,

@@ -155,6 +155,14 @@ SIGNATURES = {
     "wc_conv_narrow_out_supported": (c_int, [c_int64, c_int64, c_int64, c_int, c_int, c_int]),
     "wc_conv_narrow_out_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int,
                                        c_void_p, c_void_p]),
+    "wc_conv_narrow32_supported": (c_int, [c_int64, c_int64, c_int64, c_int, c_int, c_int]),
+    "wc_conv_wrw_narrow32_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int, c_int, c_int]),
+    "wc_conv_wrw_narrow32_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_int64, c_int64,
+                                         c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wc_conv_fwd_narrow32_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int,
+                                         c_int, c_int, c_void_p, c_void_p]),
+    "wc_conv_narrow_out_bias_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                            c_int, c_int, c_int, c_void_p, c_void_p]),
     "wc_conv_wrw_narrow_supported": (c_int, [c_int64, c_int64, c_int64, c_int, c_int, c_int]),
     "wc_conv_wrw_narrow_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int, c_int, c_int]),
     "wc_conv_wrw_narrow_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_int64, c_int64,

@@ -932,10 +932,10 @@ def narrow_wrw_supported(x, w):
     return bool(_lib.load().wc_conv_narrow64_supported(N, H, W, C, w.shape[0], k))
 
 
-def narrow_forward(x, w, bias=None, relu=False, mirrored=False):
+def narrow_forward(x, w, bias=None, relu=False, mirrored=False, wide32=False):
     """wc_conv_fwd_narrow_f32: y = conv(x, w) + bias for NHWC x with a handful of channels, w (Cout, Cin, k, k) in any dense layout.
     mirrored: w is (Cin, Cout, k, k) of the TRANSPOSED map and its taps are read back to front -- y is then the data gradient of the
-    convolution w belongs to (x = its output gradient)."""
+    convolution w belongs to (x = its output gradient).  wide32 (_NarrowLastConv only): wc_conv_fwd_narrow32_f32, the wide side in 32s."""
     lib = _lib.load()
     N, H, W, C = x.shape
     k = w.shape[2]
@@ -949,6 +949,10 @@ def narrow_forward(x, w, bias=None, relu=False, mirrored=False):
         strides = (w.stride(1), w.stride(0), w.stride(2), w.stride(3))
     y = torch.empty((N, H, W, O), dtype=torch.float32, device=x.device)
     xc = x if x.is_contiguous() else x.contiguous()
+    if wide32:
+        _lib.check(lib.wc_conv_fwd_narrow32_f32(_ptr(xc), ptr, *strides, _ptr(bias), N, H, W, C, O, k, 1 if relu else 0, _ptr(y), _stream()),
+                   "wc_conv_fwd_narrow32_f32")
+        return y
     _lib.check(lib.wc_conv_fwd_narrow_f32(_ptr(xc), ptr, *strides, _ptr(bias), N, H, W, C, O, k, 1 if relu else 0, _ptr(y), _stream()),
                "wc_conv_fwd_narrow_f32")
     return y
@@ -971,11 +975,12 @@ def narrow_out_supported(gshape, wshape, forward=False):
     return C == cw and bool(_lib.load().wc_conv_narrow_out_supported(N, H, W, cw, cn, wshape[2]))
 
 
-def narrow_out_conv(g, w, mask=None, forward=False):
+def narrow_out_conv(g, w, mask=None, forward=False, bias=None):
     """wc_conv_narrow_out_f32: the 'same' convolution of the wide NHWC fp32 tensor g down to a handful of channels.  w (Cw, Cn, k, k), any
     dense layout: the DATA GRADIENT of the layer w belongs to, g its output gradient.  forward=True: w is (Cn, Cw, k, k) and the result
     that layer's output (its taps read back to front, the channel strides exchanged).  mask (g's shape): g is read through the backward
-    of a ReLU whose pre-activation was `mask` -- the values of threshold_backward(g, mask, 0), which is never written."""
+    of a ReLU whose pre-activation was `mask` -- the values of threshold_backward(g, mask, 0), which is never written.  bias (Cn floats):
+    added to every output pixel in the same launch (wc_conv_narrow_out_bias_f32); without one, the entry and the bits it always had."""
     N, H, W, C = g.shape
     k = w.shape[2]
     if _storage_extent(w) != w.numel():
@@ -994,6 +999,12 @@ def narrow_out_conv(g, w, mask=None, forward=False):
             raise ValueError("narrow_out_conv: the mask is an fp32 tensor of g's shape")
         mask = mask if mask.is_contiguous() else mask.contiguous()
     out = torch.empty((N, H, W, cn), dtype=torch.float32, device=g.device)
+    if bias is not None:
+        if not (bias.shape == (cn,) and bias.dtype == torch.float32 and bias.is_contiguous()):
+            raise ValueError("narrow_out_conv: the bias is a dense fp32 vector, one value per output channel")
+        _lib.check(_lib.load().wc_conv_narrow_out_bias_f32(_ptr(gc), _ptr(mask), ptr, *strides, _ptr(bias), N, H, W, C, cn, k, _ptr(out),
+                                                           _stream()), "wc_conv_narrow_out_bias_f32")
+        return out
     _lib.check(_lib.load().wc_conv_narrow_out_f32(_ptr(gc), _ptr(mask), ptr, *strides, N, H, W, C, cn, k, _ptr(out), _stream()),
                "wc_conv_narrow_out_f32")
     return out
@@ -1068,19 +1079,26 @@ def narrow_in_conv(x, w, bias=None, site=None):
     return _NarrowInConv.apply(x, w, bias, site)
 
 
-def narrow_out_weight_gradient(x, gy, w):
+def narrow_out_weight_gradient(x, gy, w, wide32=False):
     """dW of a 3x3 'same' convolution with a handful of OUTPUT channels (the generator's last layer, 256 -> 3) by the same one-pass kernel with
     the operands' roles exchanged: dW[o][c][r][s] = sum_q gy[q - (r-1, s-1)][o] x[q][c] is the narrow-input gradient of a convolution that reads
-    gy (3 channels) and whose output gradient is x (256 channels), with the taps mirrored -- written through negative tap strides.  x, gy NHWC."""
+    gy (3 channels) and whose output gradient is x (256 channels), with the taps mirrored -- written through negative tap strides.  x, gy NHWC.
+    wide32 (_NarrowLastConv only): wc_conv_wrw_narrow32_f32, x's channels in 32s (and a 1x1 layer as well)."""
     lib = _lib.load()
     N, H, W, C = x.shape
     O, k = w.shape[0], w.shape[2]
     dw = torch.empty_strided(w.shape, w.stride(), dtype=torch.float32, device=w.device)
     if _storage_extent(dw) != dw.numel():
         raise ValueError("weight must be dense")
+    last = dw.data_ptr() + 4 * ((k - 1) * dw.stride(2) + (k - 1) * dw.stride(3))        # tap (k-1, k-1): the mirrored (0, 0)
+    if wide32:
+        nb = lib.wc_conv_wrw_narrow32_workspace_bytes(N, H, W, O, C, k)
+        ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+        _lib.check(lib.wc_conv_wrw_narrow32_f32(_ptr(gy), _ptr(x), N, H, W, O, C, k, ctypes.c_void_p(last), dw.stride(0), dw.stride(1),
+                                                -dw.stride(2), -dw.stride(3), None, _ptr(ws), nb, _stream()), "wc_conv_wrw_narrow32_f32")
+        return dw
     nb = lib.wc_conv_wrw_narrow_workspace_bytes(N, H, W, O, C, k)
     ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
-    last = dw.data_ptr() + 4 * ((k - 1) * dw.stride(2) + (k - 1) * dw.stride(3))        # tap (k-1, k-1): the mirrored (0, 0)
     _lib.check(lib.wc_conv_wrw_narrow_f32(_ptr(gy), _ptr(x), N, H, W, O, C, k, ctypes.c_void_p(last), dw.stride(0), dw.stride(1), -dw.stride(2),
                                           -dw.stride(3), None, _ptr(ws), nb, _stream()), "wc_conv_wrw_narrow_f32")
     return dw
@@ -1094,6 +1112,54 @@ def narrow_out_wrw_supported(x, w):
         return False
     N, H, W, C = x.shape
     return bool(_lib.load().wc_conv_wrw_narrow_supported(N, H, W, w.shape[0], C, k))
+
+
+# The generator's last layer at a width the CIFAR route above does not take (the ImageNet recipe: 32 -> 3 at 128 x 128; DESIGN.md section
+# 4.24).  A layer marked narrow_last (make_generator(narrow_last=True)) runs its forward on the narrow-output kernel with the taps mirrored
+# and the bias inside (wc_conv_narrow_out_bias_f32), its weight gradient on the one-pass kernel with the operands exchanged
+# (wc_conv_wrw_narrow32_f32) and its data gradient on the mirrored narrow forward (wc_conv_fwd_narrow32_f32): no GEMM + fold, no
+# convolution_backward, no intermediate of nine times the output.
+def narrow_last_supported(xshape, wshape):
+    """Does _NarrowLastConv take an NHWC input of this shape with this weight?  Shapes only: w (Cn, Cw, k, k) with Cn <= 4, the forward
+    on the narrow-output kernel (narrow_out_supported(forward=True)) and both gradients on the 32-wide narrow entries
+    (wc_conv_narrow32_supported: one predicate for the exchanged weight gradient and the mirrored data gradient)."""
+    if len(xshape) != 4 or len(wshape) != 4 or wshape[2] != wshape[3] or wshape[0] > 4:
+        return False
+    if not narrow_out_supported(tuple(xshape), tuple(wshape), forward=True):
+        return False
+    N, H, W, _ = xshape
+    if N * H * W * wshape[0] >= 2 ** 31:                 # (the mirrored forward's 32-bit element offset; implied by Cn <= 4 only up to 2^29 pixels)
+        return False
+    return bool(_lib.load().wc_conv_narrow32_supported(N, H, W, wshape[0], wshape[1], wshape[2]))
+
+
+class _NarrowLastConv(torch.autograd.Function):
+    """'same' convolution (1x1 or 3x3) of a wide NHWC input down to a handful of channels (narrow_last_supported), every pass on the
+    project's narrow kernels.  db = the column sums of the output gradient, the reduction _NarrowConv3x3 uses under sum_bias_grad."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias):
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = bias is not None
+        return narrow_out_conv(x, w, forward=True, bias=bias)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        g = gy if gy.is_contiguous() else gy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = narrow_forward(g, w, None, mirrored=True, wide32=True)
+        if ctx.needs_input_grad[1]:
+            dw = narrow_out_weight_gradient(x, g, w, wide32=True)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            db = g.sum(dim=(0, 1, 2))
+        return dx, dw, db
+
+
+def narrow_last_conv(x, w, bias=None):
+    """y = conv(x, w) + bias for contiguous NHWC fp32 x on the GPU and a dense w (Cn, Cw, k, k): narrow_last_supported(x.shape, w.shape)"""
+    return _NarrowLastConv.apply(x, w, bias)
 
 
 def fast_conv(x, w, bias=None, kind='same', residual=None, ragged=False, slim=False):

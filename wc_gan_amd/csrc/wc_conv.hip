@@ -1789,6 +1789,103 @@ __global__ __launch_bounds__(256) void conv_wrw_narrow_reduce_kernel(const float
     } else if (row == nrow && db) db[o] = sum;
 }
 
+// ---- the same gradient with a channel group of 32 (wc_conv_wrw_narrow32_f32 where Cout % 64 == 32) ----------------------------------------
+// The generator's last layer at 32 filters (ImageNet recipe, 32 -> 3 at 128 x 128) with the operands exchanged: "gy" is the layer's input,
+// 32 channels wide.  The body above gives a lane 16 bytes of gy and four MFMAs per pixel pair; at 32 channels three of the four and 24 of
+// 32 lanes' loads would be waste.  Here lane (i, k) loads the ONE float gy[p + k][32 grp + i] (a half-wave reads a pixel's whole 128-byte
+// row) and a pixel pair is one v_mfma_f32_32x32x2_f32.  The same pixel ranges per wave, the same LDS fold over the eight waves in wave
+// order, the same ones-row for db; a partial is 1024 floats.  Every group of such a layer is 32 wide (Cout = 96: three groups, not a
+// 64-group and a remainder): one kernel, one element map.  With 16 accumulator registers the loop keeps 16 pixel pairs in flight.
+__global__ __launch_bounds__(512, 1) void conv_wrw_narrow32_kernel(NarrowWrwArgs a)
+{
+    __shared__ float nw32_part[8 * 1024];                               // [8 waves][16 r][64 lanes]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = lane & 31, k = lane >> 5;
+    const int grp = blockIdx.y;                                         // 32 output channels
+    const bool is_tap = i < a.nrow, is_one = i == a.nrow;
+    int dy = 0, dx = 0, c = 0;
+    if (is_tap) {
+        const int tap = i / a.Cin;
+        c = i - tap * a.Cin;
+        dy = tap / a.ks - a.ks / 2; dx = tap % a.ks - a.ks / 2;
+    }
+    const unsigned HW = (unsigned)(a.H * a.W);
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    const int64_t p0 = ((int64_t)blockIdx.x * 8 + wave) * a.pix_per_wave;
+    int64_t p1 = p0 + a.pix_per_wave;
+    if (p1 > a.M) p1 = a.M;
+    const float* gyc = a.gy + grp * 32 + i;
+    constexpr int U = 16;
+    for (int64_t p = p0; p < p1; p += 2 * U) {
+        float av[U], bv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t pp = p + 2 * u + k;
+            const bool ok = pp < p1;
+            const unsigned pc = (unsigned)(ok ? pp : a.M - 1);          // clamped, not predicated (A is zero there): the loads stay in flight together
+            const unsigned n = __umulhi(pc, a.magHW) >> a.shHW, rem = pc - n * HW;
+            const unsigned yy = __umulhi(rem, a.magW) >> a.shW, xx = rem - yy * a.W;
+            const int iy = (int)yy + dy, ix = (int)xx + dx;
+            const bool inb = ok && is_tap && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
+            const float xv = a.x[inb ? ((int64_t)(n * a.H + iy) * a.W + ix) * a.Cin + c : 0];
+            av[u] = inb ? xv : ((ok && is_one) ? 1.f : 0.f);
+            bv[u] = gyc[(int64_t)pc * a.Cout];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) nw32_part[(wave * 16 + r) * 64 + lane] = acc[r];
+    __syncthreads();
+    float* out = a.partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 1024;
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const int e = tid + 512 * m;
+        float sum = nw32_part[e];
+#pragma unroll
+        for (int w = 1; w < 8; ++w) sum += nw32_part[w * 1024 + e];
+        out[e] = sum;
+    }
+}
+
+// conv_wrw_narrow_reduce_kernel for partials of 1024: element e = (r, lane) -> the same row, output channel 32 grp + (lane & 31); the same
+// eight groups of partials and the same fold.  Grid (32, Cout / 32).
+__global__ __launch_bounds__(256) void conv_wrw_narrow32_reduce_kernel(const float* __restrict__ partial, int nparts, int Cin, int ks, int nrow,
+                                                                       float* __restrict__ dw, int64_t sk, int64_t sn, int64_t sr, int64_t ss,
+                                                                       float* __restrict__ db, int Cout)
+{
+    __shared__ float red[8][32];
+    const int el = threadIdx.x & 31, pg = threadIdx.x >> 5;
+    const int e = blockIdx.x * 32 + el;                                 // < 1024
+    const float* p = partial + (int64_t)blockIdx.y * nparts * 1024 + e;
+    float sum = 0.f;
+    int z = pg;
+    for (; z + 8 * 15 < nparts; z += 8 * 16) {
+        float v[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[u] = p[(int64_t)(z + 8 * u) * 1024];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) sum += v[u];
+    }
+    for (; z < nparts; z += 8) sum += p[(int64_t)z * 1024];
+    red[pg][el] = sum;
+    __syncthreads();
+    if (pg != 0) return;
+#pragma unroll
+    for (int g = 1; g < 8; ++g) sum += red[g][el];
+    const int r = e >> 6, ln = e & 63;
+    const int row = (r & 3) + 8 * (r >> 2) + 4 * (ln >> 5);
+    const int o = blockIdx.y * 32 + (ln & 31);
+    if (o >= Cout) return;
+    if (row < nrow) {
+        const int tap = row / Cin, c = row - tap * Cin;
+        dw[c * sk + o * sn + (tap / ks) * sr + (tap % ks) * ss] = sum;
+    } else if (row == nrow && db) db[o] = sum;
+}
+
 // ---- forward of a convolution with a handful of INPUT channels (round 5): y[p][o] = sum_m A[p][m] Wm[m][o],  m = tap * Cin + c ------------
 // The critic's first convolution and shortcut on images (3 -> 128) and -- with the weight read through mirrored tap strides -- the data
 // gradient of the generator's last layer (gy with 3 channels -> dx with 256).  MIOpen's kernel (23 us at 128x32x32, 3 -> 128) is followed by
@@ -1804,8 +1901,12 @@ struct NarrowFwdArgs {
     signed char tdy[32], tdx[32], tch[32], tr[32], ts[32];     // row m of A: tap offsets, input channel, the weight's tap indices (host-made: no divisions on the device)
 };
 
-constexpr int kNarrowLd = 32 * 2 + 4;     // floats per pixel row of a wave's LDS tile (16-byte aligned, the two lane halves 16 banks apart)
 constexpr int kNarrowNQ = 2;          // 32-channel output blocks per wave: 64 channels (4 blocks took 316 registers: one wave per SIMD, 35 us)
+// floats per pixel row of a wave's LDS tile.  64 channels: 16-byte aligned, the two lane halves 16 banks apart.  32 channels (NQ = 1,
+// wc_conv_fwd_narrow32_f32): no padding -- a half-wave's ds_write_b32 is one row of 32 consecutive floats, and the four (row, column half)
+// pieces that one 16-lane group of the ds_read_b128 takes -- (0, lo) (1, hi) (2, hi) (3, lo) or (0, hi) (1, lo) (2, lo) (3, hi) -- lie
+// at 0, 48, 16, 32 or 16, 32, 0, 48 of the 64 banks: no bank twice.
+template <int NQ> constexpr int kNarrowLd = NQ == 2 ? 32 * 2 + 4 : 32 * NQ;
 // SPLIT (the critic's first block, conv._CriticFirstBlock): the float4 a lane stores to y is the unit conv_split_elem works on, so the
 // kernel also leaves the planes of act(y) for the convolution that reads y next, scaled by that reader's record -- what
 // conv_split_hist_kernel would have left after reading all of y back.  The record has kAmaxBlocks pairs and this grid G <= kAmaxBlocks
@@ -1817,27 +1918,31 @@ struct NarrowSplitArgs {
     int act; float slope; int nt;                    // split_act's convention
 };
 
-template <int KS, bool SPLIT>
+template <int KS, bool SPLIT, int NQ = kNarrowNQ>
 __device__ __forceinline__ void conv_fwd_narrow_body(const NarrowFwdArgs& a, const NarrowSplitArgs* sp)
 {
-    __shared__ __attribute__((aligned(16))) float nf_tile[4 * 32 * kNarrowLd];
+    __shared__ __attribute__((aligned(16))) float nf_tile[4 * 32 * kNarrowLd<NQ>];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 31, k = lane >> 5;
     const int grp = blockIdx.y;
+    static_assert(NQ == 1 || NQ == 2, "a wave's tile: 32 pixels x 32 or 64 channels");
+    constexpr int LD = kNarrowLd<NQ>;
+    constexpr int RL = 8 * NQ;                                       // lanes per pixel row of the tile (16 bytes each), 64 / RL rows per store
     // the workgroup's 32 x 64 slice of the weight (row m = tap * Cin + c, the bias row, zero rows) and the rows' tap tables go through LDS:
     // eight coalesced loads per thread with wave-uniform row indices (scalar table reads) instead of ~100 dependent gathers per wave
-    __shared__ float nf_w[32][32 * kNarrowNQ];
+    __shared__ float nf_w[32][32 * NQ];
     __shared__ int nf_tab[32][2];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int m = wave + 4 * j;                                  // wave-uniform
         const int kind = m < a.nrow ? 0 : (m == a.nrow ? 1 : 2);     // 0: a tap, 1: the bias row, 2: padding of K
-        const int o = grp * (32 * kNarrowNQ) + lane;
+        const int o = grp * (32 * NQ) + lane;
+        const bool col = NQ == 2 || lane < 32;                       // (a 32-channel group: the upper lanes have no column, they load and write nothing)
         float v = 0.f;
-        if (kind == 0) v = a.w[a.tch[m] * a.sk + o * a.sn + a.tr[m] * a.sr + a.ts[m] * a.ss];
-        else if (kind == 1) v = a.bias ? a.bias[o] : 0.f;
-        nf_w[m][lane] = v;
+        if (col && kind == 0) v = a.w[a.tch[m] * a.sk + o * a.sn + a.tr[m] * a.sr + a.ts[m] * a.ss];
+        else if (col && kind == 1) v = a.bias ? a.bias[o] : 0.f;
+        if (col) nf_w[m][lane] = v;
         if (lane == 0) {
             const int dy = a.tdy[m], dx = a.tdx[m];
             nf_tab[m][0] = (dy & 0xff) | ((dx & 0xff) << 8) | (kind << 16);
@@ -1846,14 +1951,14 @@ __device__ __forceinline__ void conv_fwd_narrow_body(const NarrowFwdArgs& a, con
     }
     __syncthreads();
     // this lane's KS rows of A: m = 2 s + k -> (dy, dx, kind), the element offset of the tap, the weight's fragments
-    int dyx[KS], off[KS]; float bw[KS][kNarrowNQ];
+    int dyx[KS], off[KS]; float bw[KS][NQ];
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
         const int m = 2 * s + k;
         dyx[s] = nf_tab[m][0];
         off[s] = nf_tab[m][1];
 #pragma unroll
-        for (int q = 0; q < kNarrowNQ; ++q) bw[s][q] = nf_w[m][q * 32 + i];
+        for (int q = 0; q < NQ; ++q) bw[s][q] = nf_w[m][q * 32 + i];
     }
     const unsigned HW = (unsigned)(a.H * a.W);
     const int t0 = (blockIdx.x * 4 + wave) * a.tiles_per_wave;
@@ -1882,38 +1987,38 @@ __device__ __forceinline__ void conv_fwd_narrow_body(const NarrowFwdArgs& a, con
     if (t0 < t1) gather(t0, av);
     for (int t = t0; t < t1; ++t) {
         if (t + 1 < t1) gather(t + 1, an);
-        f32x16 acc[kNarrowNQ];
+        f32x16 acc[NQ];
 #pragma unroll
-        for (int q = 0; q < kNarrowNQ; ++q)
+        for (int q = 0; q < NQ; ++q)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
 #pragma unroll
         for (int s = 0; s < KS; ++s)
 #pragma unroll
-            for (int q = 0; q < kNarrowNQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bw[s][q], acc[q], 0, 0, 0);
+            for (int q = 0; q < NQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bw[s][q], acc[q], 0, 0, 0);
         // rows = pixels (r & 3) + 8 (r >> 2) + 4 k of the tile, columns = output channel q * 32 + i of the group: through LDS, so that the
         // tile leaves as 16 bytes per lane, four whole 256-byte pixel rows per store (4 bytes per lane in 128-byte pieces ran at 2.6 TB/s)
-        float* tl = nf_tile + wave * (32 * kNarrowLd);
+        float* tl = nf_tile + wave * (32 * LD);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = (r & 3) + 8 * (r >> 2) + 4 * k;
 #pragma unroll
-            for (int q = 0; q < kNarrowNQ; ++q) {
+            for (int q = 0; q < NQ; ++q) {
                 float v = acc[q][r];
                 if (a.relu) v = fmaxf(v, 0.f);
-                tl[row * kNarrowLd + q * 32 + i] = v;
+                tl[row * LD + q * 32 + i] = v;
             }
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);         // lgkmcnt(0): the wave's own writes (no other wave touches its slice)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int row = 4 * j + (lane >> 4);
+        for (int j = 0; j < 32 * RL / 64; ++j) {
+            const int row = (64 / RL) * j + lane / RL;
             const int64_t pr = (int64_t)t * 32 + row;
-            const f32x4 v = *reinterpret_cast<const f32x4*>(tl + row * kNarrowLd + 4 * (lane & 15));
+            const f32x4 v = *reinterpret_cast<const f32x4*>(tl + row * LD + 4 * (lane & (RL - 1)));
             if constexpr (!SPLIT) {
-                if (pr < a.M) *reinterpret_cast<f32x4*>(a.y + pr * a.Cout + grp * (32 * kNarrowNQ) + 4 * (lane & 15)) = v;
+                if (pr < a.M) *reinterpret_cast<f32x4*>(a.y + pr * a.Cout + grp * (32 * NQ) + 4 * (lane & (RL - 1))) = v;
             } else if (pr < a.M) {                  // (a row past the tensor: no stores, no part in the maximum)
-                const int64_t e = pr * a.Cout + grp * (32 * kNarrowNQ) + 4 * (lane & 15);
+                const int64_t e = pr * a.Cout + grp * (32 * NQ) + 4 * (lane & (RL - 1));
                 if (sp->nt) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(a.y + e));
                 else *reinterpret_cast<f32x4*>(a.y + e) = v;
                 amax = conv_split_elem(split_act(v, sp->act, sp->slope), amax, pk.s, sp->hi, sp->lo, e >> 2);
@@ -1940,6 +2045,10 @@ __device__ __forceinline__ void conv_fwd_narrow_body(const NarrowFwdArgs& a, con
 template <int KS>
 __global__ __launch_bounds__(256, 2) void conv_fwd_narrow_kernel(NarrowFwdArgs a) { conv_fwd_narrow_body<KS, false>(a, nullptr); }
 
+// one 32-channel block per wave (wc_conv_fwd_narrow32_f32 where Cout % 64 == 32: the mirrored data gradient of a 32 -> 3 layer)
+template <int KS>
+__global__ __launch_bounds__(256, 2) void conv_fwd_narrow32_kernel(NarrowFwdArgs a) { conv_fwd_narrow_body<KS, false, 1>(a, nullptr); }
+
 template <int KS>
 __global__ __launch_bounds__(256, 2) void conv_fwd_narrow_split_kernel(NarrowFwdArgs a, NarrowSplitArgs s) { conv_fwd_narrow_body<KS, true>(a, &s); }
 
@@ -1964,12 +2073,15 @@ struct NarrowOutArgs {
     int nwg, per_xcd;                                // workgroup b of the grid works on band (b & 7) * per_xcd + (b >> 3)
     int64_t sk, sn, sr, ss;                          // w[o * sk + c * sn + r * sr + s * ss]
     unsigned magW, shW;
+    const float* bias;                               // the BIAS instantiations only: Cn floats
 };
 
 constexpr int kNarrowOutThreads = 512;
 constexpr int kNarrowOutLds = 80 * 1024;             // two workgroups per CU
 
-template <bool MASKED>
+// BIAS (wc_conv_narrow_out_bias_f32, the forward of a layer with few outputs): a.bias[c] is added to an output behind its tap sum, one fp32
+// add in the gather epilogue.  The instantiations without one keep their instructions.
+template <bool MASKED, bool BIAS = false>
 __global__ __launch_bounds__(kNarrowOutThreads) void conv_narrow_out_kernel(NarrowOutArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float no_lds[];     // [Cw][32] weight rows | [band pixels][ld] Z
@@ -2062,6 +2174,7 @@ __global__ __launch_bounds__(kNarrowOutThreads) void conv_narrow_out_kernel(Narr
                         sum += zl[((iy - z0) * a.W + ix) * a.ld + (r * a.ks + s) * a.Cn + c];
                 }
             }
+            if constexpr (BIAS) sum += a.bias[c];
             op[c] = sum;
         }
     }
@@ -2689,10 +2802,12 @@ static int wrw_splits(const wc_conv_geom* g, int* tile)
 
 int wc_conv_wrw_narrow_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize);
 int wc_conv_narrow64_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize);
+int wc_conv_narrow32_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize);
 
 // the argument block and grid of the narrow forward (both entries below: one source for the tiling)
 static dim3 narrow_fwd_args(NarrowFwdArgs& a, const float* x, const float* w, int64_t stride_k, int64_t stride_n, int64_t stride_r,
-                            int64_t stride_s, const float* bias, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize, int relu, float* y)
+                            int64_t stride_s, const float* bias, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize, int relu, float* y,
+                            int nq = kNarrowNQ)
 {
     a.x = x; a.w = w; a.bias = bias; a.y = y;
     a.N = (int)N; a.H = (int)H; a.W = (int)W; a.Cin = Cin; a.Cout = Cout; a.ks = ksize; a.nrow = ksize * ksize * Cin; a.relu = relu;
@@ -2707,9 +2822,12 @@ static dim3 narrow_fwd_args(NarrowFwdArgs& a, const float* x, const float* w, in
     a.M = N * H * W;
     a.ntiles = (int)((a.M + 31) / 32);
     a.tiles_per_wave = (a.ntiles + 1023) / 1024;           // x Cout / 64 workgroup columns: ~2 waves per SIMD at Cout = 128 (three, at 166 registers: 32.8 against 30.7 us)
+    // (32-channel columns, wc_conv_fwd_narrow32_f32: a 32 -> 3 layer's data gradient has ONE column -- 4096 waves over the columns, four
+    // per SIMD, to keep the stores of a pass that only writes in flight)
+    if (nq == 1) a.tiles_per_wave = (int)(((int64_t)a.ntiles * (Cout / 32) + 4095) / 4096);
     if (a.tiles_per_wave < 1) a.tiles_per_wave = 1;
     const int nwg = (a.ntiles + 4 * a.tiles_per_wave - 1) / (4 * a.tiles_per_wave);
-    return dim3(nwg, Cout / (32 * kNarrowNQ));
+    return dim3(nwg, Cout / (32 * nq));
 }
 
 int wc_conv_fwd_narrow_f32(const float* x, const float* w, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
@@ -2726,6 +2844,27 @@ int wc_conv_fwd_narrow_f32(const float* x, const float* w, int64_t stride_k, int
     else if (ks2 <= 10) hipLaunchKernelGGL(conv_fwd_narrow_kernel<10>, grid, dim3(256), 0, st, a);
     else if (ks2 <= 14) hipLaunchKernelGGL(conv_fwd_narrow_kernel<14>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(conv_fwd_narrow_kernel<16>, grid, dim3(256), 0, st, a);
+    return (int)hipGetLastError();
+}
+
+// The same contract on the wider shape set (wc_conv_narrow32_supported).  Cout % 64 == 0: wc_conv_fwd_narrow_f32's launch.  Cout % 64 == 32:
+// conv_fwd_narrow32_kernel, one 32-channel block per wave, on every column of the layer.
+int wc_conv_fwd_narrow32_f32(const float* x, const float* w, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s,
+                             const float* bias, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize, int relu, float* y, wc_stream_t stream)
+{
+    if (!x || !w || !y) return WC_ERR_ARG;
+    // (the kernel's 32-bit element offset pc * Cin + off)
+    if (!wc_conv_narrow32_supported(N, H, W, Cin, Cout, ksize) || N * H * W * Cin >= ((int64_t)1 << 31)) return WC_ERR_SHAPE;
+    if ((Cout & 63) == 0) return wc_conv_fwd_narrow_f32(x, w, stride_k, stride_n, stride_r, stride_s, bias, N, H, W, Cin, Cout, ksize, relu, y, stream);
+    hipStream_t st = (hipStream_t)stream;
+    NarrowFwdArgs a = {};
+    const dim3 grid = narrow_fwd_args(a, x, w, stride_k, stride_n, stride_r, stride_s, bias, N, H, W, Cin, Cout, ksize, relu, y, 1);
+    const int ks2 = (a.nrow + 2) / 2;
+    if (ks2 <= 2) hipLaunchKernelGGL(conv_fwd_narrow32_kernel<2>, grid, dim3(256), 0, st, a);
+    else if (ks2 <= 5) hipLaunchKernelGGL(conv_fwd_narrow32_kernel<5>, grid, dim3(256), 0, st, a);
+    else if (ks2 <= 10) hipLaunchKernelGGL(conv_fwd_narrow32_kernel<10>, grid, dim3(256), 0, st, a);
+    else if (ks2 <= 14) hipLaunchKernelGGL(conv_fwd_narrow32_kernel<14>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(conv_fwd_narrow32_kernel<16>, grid, dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
 
@@ -2778,6 +2917,15 @@ int wc_conv_narrow64_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cou
     if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3)) return 0;
     if (ksize * ksize * Cin >= 32 || (Cout & 63)) return 0;
     if (W < 2) return 0;                             // the multiply-shift division wants divisors >= 2 (conv_geom_ok's line)
+    return N * H * W < ((int64_t)1 << 31) ? 1 : 0;
+}
+
+// wc_conv_narrow64_supported with Cout in 32s: the whole set of the narrow32 entries
+int wc_conv_narrow32_supported(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize)
+{
+    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3)) return 0;
+    if (ksize * ksize * Cin >= 32 || (Cout & 31)) return 0;
+    if (W < 2) return 0;
     return N * H * W < ((int64_t)1 << 31) ? 1 : 0;
 }
 
@@ -2842,6 +2990,40 @@ int wc_conv_wrw_narrow_masked_f32(const float* x, const float* gy, const float* 
     return wrw_narrow64(x, gy, mask, N, H, W, Cin, Cout, ksize, dw, stride_k, stride_n, stride_r, stride_s, db, ws, ws_bytes, stream);
 }
 
+// Cout % 64 == 0: wc_conv_wrw_narrow64_f32's size and launches.  Cout % 64 == 32: every group 32 wide, one partial of 1024 floats per
+// (pixel range, group) -- the same bytes per channel.
+size_t wc_conv_wrw_narrow32_workspace_bytes(int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize)
+{
+    if (!wc_conv_narrow32_supported(N, H, W, Cin, Cout, ksize)) return 0;
+    if ((Cout & 63) == 0) return wc_conv_wrw_narrow64_workspace_bytes(N, H, W, Cin, Cout, ksize);
+    int64_t ppw;
+    return (size_t)narrow_wrw_parts(N * H * W, &ppw) * (Cout / 32) * 1024 * sizeof(float);
+}
+
+int wc_conv_wrw_narrow32_f32(const float* x, const float* gy, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize,
+                             float* dw, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s, float* db,
+                             void* ws, size_t ws_bytes, wc_stream_t stream)
+{
+    if (!x || !gy || !dw || !ws) return WC_ERR_ARG;
+    if (!wc_conv_narrow32_supported(N, H, W, Cin, Cout, ksize)) return WC_ERR_SHAPE;
+    if ((Cout & 63) == 0)
+        return wrw_narrow64(x, gy, nullptr, N, H, W, Cin, Cout, ksize, dw, stride_k, stride_n, stride_r, stride_s, db, ws, ws_bytes, stream);
+    if (ws_bytes < wc_conv_wrw_narrow32_workspace_bytes(N, H, W, Cin, Cout, ksize)) return WC_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    NarrowWrwArgs a = {};
+    a.x = x; a.gy = gy; a.partial = (float*)ws;
+    a.N = (int)N; a.H = (int)H; a.W = (int)W; a.Cin = Cin; a.Cout = Cout; a.ks = ksize; a.nrow = ksize * ksize * Cin;
+    magic_u31((unsigned)(H * W), &a.magHW, &a.shHW);
+    magic_u31((unsigned)W, &a.magW, &a.shW);
+    a.M = N * H * W;
+    const int nparts = (int)narrow_wrw_parts(a.M, &a.pix_per_wave);
+    const int ngrp = Cout / 32;
+    hipLaunchKernelGGL(conv_wrw_narrow32_kernel, dim3(nparts, ngrp), dim3(512), 0, st, a);
+    hipLaunchKernelGGL(conv_wrw_narrow32_reduce_kernel, dim3(32, ngrp), dim3(256), 0, st, (const float*)ws, nparts, Cin, ksize, a.nrow,
+                       dw, stride_k, stride_n, stride_r, stride_s, db, Cout);
+    return (int)hipGetLastError();
+}
+
 int wc_conv_wrw_narrow_f32(const float* x, const float* gy, int64_t N, int64_t H, int64_t W, int Cin, int Cout, int ksize,
                            float* dw, int64_t stride_k, int64_t stride_n, int64_t stride_r, int64_t stride_s, float* db,
                            void* ws, size_t ws_bytes, wc_stream_t stream)
@@ -2904,6 +3086,31 @@ int wc_conv_narrow_out_f32(const float* g, const float* mask, const float* w, in
     const dim3 grid((unsigned)(8 * a.per_xcd));
     if (mask) hipLaunchKernelGGL(conv_narrow_out_kernel<true>, grid, dim3(kNarrowOutThreads), lds, st, a);
     else hipLaunchKernelGGL(conv_narrow_out_kernel<false>, grid, dim3(kNarrowOutThreads), lds, st, a);
+    return (int)hipGetLastError();
+}
+
+// wc_conv_narrow_out_f32 with bias[c] added to each output behind its tap sum; bias == nullptr: that entry itself
+int wc_conv_narrow_out_bias_f32(const float* g, const float* mask, const float* w, int64_t stride_k, int64_t stride_n, int64_t stride_r,
+                                int64_t stride_s, const float* bias, int64_t N, int64_t H, int64_t W, int Cw, int Cn, int ksize, float* out,
+                                wc_stream_t stream)
+{
+    if (!bias) return wc_conv_narrow_out_f32(g, mask, w, stride_k, stride_n, stride_r, stride_s, N, H, W, Cw, Cn, ksize, out, stream);
+    if (!g || !w || !out) return WC_ERR_NULL;
+    NarrowOutArgs a = {};
+    if (!narrow_out_plan(a, N, H, W, Cw, Cn, ksize)) return WC_ERR_SHAPE;
+    if (((uintptr_t)g | (uintptr_t)mask) & 15) return WC_ERR_ARG;
+    a.g = g; a.mask = mask; a.w = w; a.out = out; a.bias = bias;
+    a.sk = stride_k; a.sn = stride_n; a.sr = stride_r; a.ss = stride_s;
+    hipStream_t st = (hipStream_t)stream;
+    const int rows = a.R + 2 * (ksize / 2);
+    const size_t lds = ((size_t)Cw * 32 + (size_t)rows * a.W * a.ld) * sizeof(float);
+    const void* kernel = mask ? reinterpret_cast<const void*>(conv_narrow_out_kernel<true, true>)
+                              : reinterpret_cast<const void*>(conv_narrow_out_kernel<false, true>);
+    hipError_t e = wc_set_max_lds(kernel, lds);
+    if (e != hipSuccess) return (int)e;
+    const dim3 grid((unsigned)(8 * a.per_xcd));
+    if (mask) hipLaunchKernelGGL((conv_narrow_out_kernel<true, true>), grid, dim3(kNarrowOutThreads), lds, st, a);
+    else hipLaunchKernelGGL((conv_narrow_out_kernel<false, true>), grid, dim3(kNarrowOutThreads), lds, st, a);
     return (int)hipGetLastError();
 }
 

@@ -107,7 +107,7 @@ class Conv2D(nn.Module):
 
     def __init__(self, in_channels, filters, kernel_size=(3, 3), use_bias=True, name=None, spectral=False,
                  spectral_iterations=1, fully_diff_spectral=False, conv_singular=True, stride=1, ragged_conv=False, slim_conv=False,
-                 slim_blocks=False):
+                 slim_blocks=False, narrow_last=False):
         super().__init__()
         # ragged_conv (ours): the block kernels may take this layer at a grid whose N*H*W is a multiple of 32 but not of 128, on a partial
         # last tile (conv.supported(ragged=True)); off, the layer keeps the routes it always had
@@ -120,6 +120,10 @@ class Conv2D(nn.Module):
         # take this layer as 'same' or 'down3' at channel widths that are multiples of 64 (conv.supported(blocks=True)), and an image layer
         # takes its data gradient on the narrow-output kernel (conv.NARROW_OUT)
         self.slim_blocks = bool(slim_blocks)
+        # narrow_last (ours): make_generator(narrow_last=True) sets it on Generator.Final alone -- a last layer
+        # the CIFAR route below does not reach (32 -> 3 at 128 x 128) runs all three passes on the narrow kernels (conv._NarrowLastConv)
+        # where _narrow_last_route says so; off, the layer keeps the route and the bits it always had
+        self.narrow_last = bool(narrow_last)
         k = kernel_size if isinstance(kernel_size, int) else kernel_size[0]
         if stride not in (1, 2) or (stride == 2 and k != 4):
             raise ValueError(f"Conv2D: stride 2 is built for the 4x4 kernel ('same' = padding 1), not {k}x{k} / {stride}")
@@ -180,11 +184,23 @@ class Conv2D(nn.Module):
                 return y
         return self.forward(F.leaky_relu(x, negative_slope), _w=w)
 
+    def _narrow_last_route(self, x):
+        """Does this call run on conv._NarrowLastConv?  The mark, the GPU, fp32, contiguous NHWC, no spectral norm, a dense weight, a
+        stride-1 layer the three narrow kernels take (conv.narrow_last_supported)."""
+        c = self.conv
+        return (getattr(self, 'narrow_last', False) and self.kind == 'same' and not hasattr(c, 'normalized_weight') and x.is_cuda and x.dim() == 4
+                and x.dtype == torch.float32 and c.weight.dtype == torch.float32 and x.is_contiguous()
+                and (c.bias is None or c.bias.dtype == torch.float32)
+                and fast_conv_mod._storage_extent(c.weight) == c.weight.numel()
+                and fast_conv_mod.narrow_last_supported(tuple(x.shape), tuple(c.weight.shape)))
+
     def forward(self, x, _w=None):
         c = self.conv
         st = split_of(x)
         if st is not None:      # the block input as pre-split planes: the convolution reads those (weight and bias folded)
             return fast_conv_mod.split_conv(x, st, self._weight() if _w is None else _w, c.bias, site=self)
+        if getattr(self, 'narrow_last', False) and self._narrow_last_route(x):
+            return fast_conv_mod.narrow_last_conv(x, c.weight, c.bias)
         if (c.out_channels <= 4 and tuple(c.kernel_size) == (3, 3) and not hasattr(c, 'normalized_weight')
                 and x.is_cuda and x.is_contiguous()):
             return _NarrowConv3x3.apply(x, c.weight, c.bias, getattr(self, 'sum_bias_grad', False))
@@ -470,7 +486,7 @@ class DCBlockUp(nn.Module):
 class Generator(nn.Module):
     def __init__(self, input_noise_shape, output_channels, first_block_shape, block_sizes, resamples,
                  block_norm_layer, last_norm_layer, conv_layer, dense_spectral, concat_cls, number_of_classes, arch,
-                 conditional, ragged_conv=False):
+                 conditional, ragged_conv=False, narrow_last=False):
         super().__init__()
         self.first_block_shape = tuple(int(v) for v in first_block_shape)
         self.conditional = conditional
@@ -503,6 +519,7 @@ class Generator(nn.Module):
         self.final_conv = conv_layer(ch, output_channels, (3, 3), name='Generator.Final')
         if arch == 'dcgan':     # (_NarrowConv3x3.backward: the bias gradient without a convolution operator)
             self.final_conv.sum_bias_grad = True
+        self.final_conv.narrow_last = bool(narrow_last)         # the mark of this layer only (Conv2D._narrow_last_route)
 
     def forward(self, z, cls=None):
         y = z
@@ -529,10 +546,10 @@ def make_generator(input_noise_shape=(128,), output_channels=3, input_cls_shape=
                    last_norm='u', last_after_norm='cs', gan_type=None, arch='res',
                    spectral=False, fully_diff_spectral=False, spectral_iterations=1, conv_singular=True,
                    process_group=None, fused_batch_norm=False, decomposition='cholesky', ragged_conv=False,
-                   slim_conv=False):
+                   slim_conv=False, narrow_last=False):
     """Same keyword surface as generator.py:93-98; returns an nn.Module called as G(z) or G(z, cls).
     fused_batch_norm, decomposition: see create_norm.  ragged_conv, slim_conv (ours, default False): mark every convolution layer -- see
-    Conv2D."""
+    Conv2D.  narrow_last (ours, default False): marks Generator.Final only, either arch -- see Conv2D.narrow_last."""
     assert arch in ['res', 'dcgan']
     if spectral and (block_after_norm not in ('uconv', 'ucs', 'n') or last_after_norm not in ('uconv', 'ucs', 'n')):
         raise NotImplementedError("spectral-normalised conditional coloring (SNConditionalConv11/SNFactorizedConv11) "
@@ -544,4 +561,4 @@ def make_generator(input_noise_shape=(128,), output_channels=3, input_cls_shape=
     last_norm_layer = mk(last_norm, last_after_norm)
     return Generator(input_noise_shape, output_channels, first_block_shape, block_sizes, resamples,
                      block_norm_layer, last_norm_layer, conv_layer, bool(spectral), concat_cls, number_of_classes, arch,
-                     conditional=gan_type is not None, ragged_conv=bool(ragged_conv))
+                     conditional=gan_type is not None, ragged_conv=bool(ragged_conv), narrow_last=bool(narrow_last))

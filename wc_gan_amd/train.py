@@ -652,10 +652,30 @@ def slim_blocks_config(config, on=True):
     """The same recipe with every convolution layer of the CRITIC marked slim_blocks (make_discriminator(slim_blocks=True), DESIGN.md
     section 4.23): its 64-wide block layers run on the block kernels and the fused critic nodes, its image layers take their data gradient
     on the narrow-output kernel.  The generator is left alone.  A copy of any entry, the entry itself is left alone; on=False: the mark
-    off.  The shipping form of the ImageNet recipe is slim_blocks_config(IMAGENET_CONFIGS['imagenet_cond_sa'], IMAGENET_SLIM_BLOCKS_SHIPS)."""
+    off.  The shipping form of the ImageNet recipe is
+    narrow_last_config(slim_blocks_config(IMAGENET_CONFIGS['imagenet_cond_sa'], IMAGENET_SLIM_BLOCKS_SHIPS), IMAGENET_NARROW_LAST_SHIPS):
+    this helper's copy with the generator's last layer marked by narrow_last_config below."""
     import copy
     out = copy.deepcopy(config)
     out['discriminator'].update(slim_blocks=bool(on))
+    return out
+
+
+# profiles/imagenet_last_step.json (tools/imagenet_last_step.py: the captured G+D step at batch 64 with Generator.Final marked narrow_last
+# against the same networks with the mark off, both other marks on in both legs, 7 alternating rounds; DESIGN.md section 4.24).  The rule of
+# sections 4.22 / 4.23: True only if the marked step is faster in every round.
+IMAGENET_NARROW_LAST_SHIPS = True
+
+
+def narrow_last_config(config, on=True):
+    """The same recipe with the GENERATOR's last layer, Generator.Final, marked narrow_last (make_generator(narrow_last=True), DESIGN.md
+    section 4.24): its forward, weight gradient and data gradient run on the narrow kernels (conv._NarrowLastConv) instead of the GEMM + fold
+    and convolution_backward.  No other layer and not the critic.  A copy of any entry, the entry itself is left alone; on=False: the mark
+    off.  The shipping form of the ImageNet recipe is
+    narrow_last_config(slim_blocks_config(IMAGENET_CONFIGS['imagenet_cond_sa'], IMAGENET_SLIM_BLOCKS_SHIPS), IMAGENET_NARROW_LAST_SHIPS)."""
+    import copy
+    out = copy.deepcopy(config)
+    out['generator'].update(narrow_last=bool(on))
     return out
 
 
